@@ -11,7 +11,17 @@ the step ends with the config-3 exchange: an all-gather of the per-crop
 logits and the video score on every rank.  Whole-job crops/s = N*256*K /
 max-over-ranks time of K steps.
 
-Also printed on the same JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what that
+headline needs: set up, W warm-up steps, K timed steps, one JSON line with the
+throughput and `ms_per_step`.  `--dump-outputs DIR` also writes what the last
+timed step returned to its caller (DIR/logits.npy, DIR/score.npy; float32) so
+that two builds can be compared output for output: the inputs are the same
+from run to run.
+
+With `--full` the same JSON line also carries the parity of the timed batch
+against the reference's fp32 golden, per-stage times, the same measurement in
+the other 16-bit dtype with `parity_grade`, configs 3/4/5, the RepBn8 variant
+(each with its own --no-* switch) and:
   roofline      - the dominant conv kernel's achieved MFMA TFLOP/s (algorithmic
                   FLOPs per launch / its average event-timed duration) vs the
                   bf16/fp16 dense peak;
@@ -571,6 +581,13 @@ def main():
     ap.add_argument("--dist-check", action="store_true",
                     help="launch + rendezvous + rank all-gather only, no measurement (the N>1 launcher's CPU test "
                          "with FAC_DIST_BACKEND=gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: golden parity, per-stage and roofline figures, "
+                         "the other 16-bit dtype, configs 3/4/5, the RepBn8 variant and the CPU baseline (each "
+                         "has its own --no-* switch); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (logits.npy, score.npy; "
+                         "float32) into DIR")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256)
@@ -661,7 +678,9 @@ def main():
         return
 
     sd = make_state_dict(0)
-    headline = cvit_measurement(args, args.dtype, dev, world, rank, sd, keep_model=not args.no_video)
+    full = args.full
+    headline = cvit_measurement(args, args.dtype, dev, world, rank, sd, keep_model=full and not args.no_video,
+                                full=full, dump_dir=args.dump_outputs)
     r = headline
     value = r["value"]
     peak = PEAK_TFLOPS[args.dtype]
@@ -689,10 +708,15 @@ def main():
                    **({"options": args.opt} if args.opt else {})},
         "mfma_roofline_fraction": round(value * FLOP_PER_CROP / (world * peak * 1e12), 4),
         "launch": launch,
-        "parity": r["parity"],
-        "roofline": r["roofline"],
-        "stage_ms": r["stage_ms"],
     }
+    if not full:
+        # the plain run ends here: the headline line, nothing measured beside it
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    line.update(parity=r["parity"], roofline=r["roofline"], stage_ms=r["stage_ms"])
     # the same measurement in fp16 (same MFMA rate on gfx950): the dtype that
     # meets the north star's 1e-3 per-frame bar
     if not args.no_fp16_line:
@@ -766,11 +790,23 @@ def parity_vs_golden(logits: torch.Tensor, B: int, rank: int):
             "bar": 1e-3, "meets_bar": dp <= 1e-3}
 
 
-def cvit_measurement(args, dtype: str, dev, world: int, rank: int, sd, keep_model: bool):
+def dump_outputs(dump_dir, logits: torch.Tensor, score: torch.Tensor):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    .npy files: this rank's per-crop logits (B, 2) and the video score over
+    the step's crops (a scalar; over every rank's crops at N > 1)."""
+    d = Path(dump_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "logits.npy", logits.detach().float().cpu().numpy().astype(np.float32))
+    np.save(d / "score.npy", score.detach().float().cpu().numpy().astype(np.float32))
+
+
+def cvit_measurement(args, dtype: str, dev, world: int, rank: int, sd, keep_model: bool, full: bool = True,
+                     dump_dir=None):
     """Config 2 (BASELINE.json configs[1]) at `dtype`: K timed steps of the
     CViT forward over B=256 HBM-resident crops (after W warm-up steps),
-    pipelined by default; returns throughput, the dominant kernel's roofline,
-    per-stage times and the parity of the last timed batch."""
+    pipelined by default; returns throughput and, with `full`, the dominant
+    kernel's roofline, per-stage times and the parity of the last timed
+    batch.  With `dump_dir` rank 0 writes the last timed step's outputs."""
     lib = _lib.load()
     from fac_fake_amd.cvit import CViT
     B = args.batch
@@ -869,7 +905,7 @@ def cvit_measurement(args, dtype: str, dev, world: int, rank: int, sd, keep_mode
     kstep[0] = 0
     # hipEvents around every fused-stem launch of the timed region (pipelined
     # steps are eager launches; a captured graph cannot hold them)
-    stem_events = pipelined and not args.no_fuse and not args.stem_chunk
+    stem_events = full and pipelined and not args.no_fuse and not args.stem_chunk
     if stem_events:
         model.set_option("stem_events", 1)
     torch.cuda.synchronize(dev)
@@ -885,7 +921,9 @@ def cvit_measurement(args, dtype: str, dev, world: int, rank: int, sd, keep_mode
         dist.barrier()
     elapsed = time.perf_counter() - t0
     last_logits = logits_pp[(args.steps - 1) & 1] if pipelined else logits
-    parity = parity_vs_golden(last_logits, B, rank)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last_logits, score)
+    parity = parity_vs_golden(last_logits, B, rank) if full else None
     stem_ms_timed, stem_n = None, 0
     if stem_events:
         avg, cnt = ctypes.c_float(), ctypes.c_int()
@@ -896,6 +934,17 @@ def cvit_measurement(args, dtype: str, dev, world: int, rank: int, sd, keep_mode
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if not full:
+        out = {"value": world * B * args.steps / elapsed, "elapsed": elapsed, "graph": graph is not None,
+               "pipelined": pipelined}
+        torch.cuda.synchronize(dev)
+        if keep_model:
+            out["model"] = model
+        else:
+            model._release()
+            del model
+        return out
 
     # per-stage event timing of one eager forward (same kernels, same stream)
     stage_ms = (ctypes.c_float * 20)()

@@ -9,7 +9,7 @@ if [ -n "$TESTK" ]; then
   timeout -k 10 300 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread -k "$TESTK" > gpurun_out/ab_pytest.log 2>&1 || { tail -30 gpurun_out/ab_pytest.log; exit 1; }
   tail -1 gpurun_out/ab_pytest.log
 fi
-ARGS="--steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-fp16-line --no-video --no-s3d --no-resvitkan --no-repbn8"
+ARGS="--full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-fp16-line --no-video --no-s3d --no-resvitkan --no-repbn8"
 IFS=';' read -ra AR <<< "$ARMS"
 for rep in $(seq 1 ${REPS:-2}); do
 for arm in "${AR[@]}"; do
