@@ -9,7 +9,7 @@ chunks of 32 and reduces the per-crop sigmoids to one score
 CSV (:341-343, "label" is the score) and, with a metadata file, an accuracy
 (:346-371).
 
-Video decoding (cv2) and face detection (dlib HOG / BlazeFace / MTCNN) are
+Video decoding (cv2) and the CPU face detectors (dlib HOG / MTCNN) are
 outside this path (only the crop/resize is in scope),
 so a "video file" here is the decoded video plus its face locations: an
 ``.npz`` holding
@@ -18,6 +18,10 @@ so a "video file" here is the decoded video plus its face locations: an
 * ``face_locations``: int32 [n, 5] = (frame, top, right, bottom, left), what
   ``face_recognition.face_locations(frame)`` returns per frame, or ``boxes``:
   int32 [n, 5] = (frame, left, top, right, bottom).
+
+With ``--detect`` (``load_detector()``) a file without either list is scored
+through the GPU BlazeFace detector (fac_fake_amd/blazeface.py), the
+reference's third detector.
 
 From there everything runs on the GPU (fac_fake_amd/video.py): the frame
 schedule of :165-198, crop + INTER_AREA + channel swap (``fac_crop_resize_u8``),
@@ -41,14 +45,15 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from fac_fake_amd.prediction import (label, non_empty, pre_process_prediction, pred_sig,  # noqa: E402,F401
                                      pred_tensor)
-from fac_fake_amd.video import (MAX_CROPS_REFERENCE, crop_faces, predict_video, score_selected,  # noqa: E402
-                                select_reference)
+from fac_fake_amd.video import (MAX_CROPS_REFERENCE, crop_faces, predict_video, predict_video_detect,  # noqa: E402
+                                score_selected, select_reference)
 
 mean = [0.485, 0.456, 0.406]    # cvit_prediction.py:41 (fused into conv1 here)
 std = [0.229, 0.224, 0.225]     # cvit_prediction.py:42
 sample = "."                    # folder of videos (cvit_prediction.py:50)
 save_csv_path = "./wprediction/cvit.csv"   # :54
 model = None                    # set by load_model() (the reference builds it at import, :62-70)
+detector = None                 # set by load_detector(): scores videos that carry no face boxes
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
 
@@ -74,13 +79,33 @@ def load_model(weights: str | None = None, dtype: str = "fp16", dev: str | None 
     return m
 
 
+DETECTOR_WEIGHTS = Path(__file__).resolve().parent / "tests" / "golden" / "blazeface_weights.npz"
+
+
+def load_detector(weights: str | None = None, anchors: str | None = None, dev: str | None = None):
+    """``BlazeFace()`` + ``load_weights`` + ``load_anchors`` as the reference's
+    ``FaceExtractor`` users set it up.  ``weights``: ``blazeface.pth``,
+    ``anchors``: ``anchors.npy``; None for either takes the reference's trained
+    weights / anchors shipped as tests/golden/blazeface_weights.npz."""
+    global detector
+    from fac_fake_amd.blazeface import BlazeFace
+    d = BlazeFace().to(dev or device)
+    d.load_weights(weights or DETECTOR_WEIGHTS)
+    d.load_anchors(anchors or DETECTOR_WEIGHTS)      # the shipped anchors are the reference's anchors.npy
+    detector = d
+    return d
+
+
 def read_video(filename: str):
     """The decoded video container: (frames uint8 [F,H,W,3] BGR, boxes int32
-    [n,5] as (frame, left, top, right, bottom))."""
+    [n,5] as (frame, left, top, right, bottom)); boxes is None for a file with
+    neither ``boxes`` nor ``face_locations`` when a detector is loaded."""
     with np.load(filename, allow_pickle=False) as z:
         frames = z["frames"]
         if "boxes" in z:
             boxes = z["boxes"].astype(np.int32).reshape(-1, 5)
+        elif "face_locations" not in z and detector is not None:
+            boxes = None
         else:
             fl = z["face_locations"].astype(np.int32).reshape(-1, 5)    # frame, top, right, bottom, left
             boxes = np.stack([fl[:, 0], fl[:, 4], fl[:, 1], fl[:, 2], fl[:, 3]], 1).astype(np.int32)
@@ -110,6 +135,8 @@ def predict(filename, mtcnn=None, mode: str = "reference"):
     if model is None:
         raise RuntimeError("call load_model() first (the reference builds its model at import)")
     frames, boxes = read_video(filename)
+    if boxes is None:
+        return predict_video_detect(model, detector, frames, mode=mode)
     # host frames: predict_video uploads only the frames its crops come from
     return predict_video(model, frames, boxes, mode=mode)
 
@@ -130,6 +157,8 @@ def predict_on_video(dfdc_filenames, num_workers, batch: int = 256):
 
     def load(i):
         frames, boxes = read_video(os.path.join(sample, dfdc_filenames[i]))
+        if boxes is None:   # no boxes in the file: found by the detector, on the calling thread
+            return frames, None
         return select_reference(frames, boxes)
 
     # read-ahead is bounded: at most num_workers + 1 loaded videos wait for
@@ -150,6 +179,8 @@ def predict_on_video(dfdc_filenames, num_workers, batch: int = 256):
     predictions, group, ncrops = [], [], 0
     with ThreadPoolExecutor(max_workers=workers) as ex:
         for item in items(ex):
+            if item[1] is None:
+                item = select_reference(item[0], _detect_reference(item[0]))
             if group and ncrops + len(item[1]) > batch:
                 predictions += score_selected(model, group, batch)
                 group, ncrops = [], 0
@@ -158,6 +189,18 @@ def predict_on_video(dfdc_filenames, num_workers, batch: int = 256):
         if group:
             predictions += score_selected(model, group, batch)
     return predictions
+
+
+def _detect_reference(frames) -> np.ndarray:
+    """The detector's boxes on the frames the reference schedule reads."""
+    from fac_fake_amd.video import detect_faces, frame_indices
+    ids = sorted(set(frame_indices(int(frames.shape[0]))))
+    if not ids:
+        return np.zeros((0, 5), np.int32)
+    sub = torch.as_tensor(np.ascontiguousarray(np.asarray(frames)[ids])).to(device)
+    boxes = detect_faces(detector, sub)
+    boxes[:, 0] = np.asarray(ids, np.int32)[boxes[:, 0]]
+    return boxes
 
 
 def real_or_fake(filenames, predictions):
@@ -201,9 +244,15 @@ def main(argv=None):
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--metadata", default=None, help="json {filename: 0/1} for the accuracy")
     ap.add_argument("--num-workers", type=int, default=1)
+    ap.add_argument("--detect", action="store_true",
+                    help="find the faces of videos that carry no boxes with the GPU BlazeFace detector")
+    ap.add_argument("--detector-weights", default=None, help="blazeface.pth (default: the shipped trained weights)")
+    ap.add_argument("--detector-anchors", default=None, help="anchors.npy (with --detector-weights)")
     args = ap.parse_args(argv)
     sample, save_csv_path = args.sample, args.csv
     load_model(args.weights, args.dtype)
+    if args.detect:
+        load_detector(args.detector_weights, args.detector_anchors)
     filenames = sorted(x for x in os.listdir(sample) if x.endswith(".npz"))
     predictions = predict_on_video(filenames, num_workers=args.num_workers)
     print(predictions)
@@ -215,7 +264,7 @@ def main(argv=None):
     return predictions
 
 
-__all__ = ["MAX_CROPS_REFERENCE", "face_face_rec", "load_model", "non_empty", "pre_process_prediction", "pred_sig",
+__all__ = ["MAX_CROPS_REFERENCE", "face_face_rec", "load_detector", "load_model", "non_empty", "pre_process_prediction", "pred_sig",
            "pred_tensor", "predict", "predict_on_video", "prediction_accuracy", "read_video", "real_or_fake",
            "write_predictions"]
 
