@@ -621,6 +621,62 @@ class KANLinearLayer:
         return y
 
 
+class ContextAdd:
+    """GCNet context block (ContextBlock3d, 'avg' pooling, 'channel_add') for
+    fac_context_add: global mean over (T, H, W), Conv1x1x1(c -> p) +
+    LayerNorm([p,1,1,1]) + ReLU6 + Conv1x1x1(p -> c), broadcast add.  Holds the
+    six fp32 tensors on the device (w3 transposed to [p][c], fac_ops.h)."""
+
+    ROUTES = {"auto": 0, "clip": 1, "split": 2}
+
+    def __init__(self, w0, b0, ln_w, ln_b, w3, b3, *, eps: float = 1e-5, dtype: str, device):
+        f = lambda t: t.detach().to("cpu", torch.float32)  # noqa: E731
+        w0, w3 = f(w0), f(w3)
+        self.p, self.c = int(w0.shape[0]), int(w0.shape[1])
+        w0, w3 = w0.reshape(self.p, self.c), w3.reshape(self.c, self.p)
+        if f(b0).numel() != self.p or f(ln_w).numel() != self.p or f(ln_b).numel() != self.p or f(b3).numel() != self.c:
+            raise ValueError("ContextAdd: weight shapes do not describe Conv(c->p) + LayerNorm(p) + Conv(p->c)")
+        self.dtype_name, self.eps = dtype, float(eps)
+        self.w0 = w0.contiguous().to(device)
+        self.b0 = f(b0).reshape(self.p).contiguous().to(device)
+        self.ln_w = f(ln_w).reshape(self.p).contiguous().to(device)
+        self.ln_b = f(ln_b).reshape(self.p).contiguous().to(device)
+        self.w3t = w3.t().contiguous().to(device)
+        self.b3 = f(b3).reshape(self.c).contiguous().to(device)
+
+    def __call__(self, x: torch.Tensor, out: torch.Tensor | None = None, inplace: bool = False, route: int = 0,
+                 return_term: bool = False):
+        if x.dtype != TORCH16[self.dtype_name] or x.dim() < 3 or x.shape[-1] != self.c or not x.is_contiguous():
+            raise ValueError(f"ContextAdd: expected a contiguous {self.dtype_name} [N, ..., {self.c}] tensor, "
+                             f"got {x.dtype} {tuple(x.shape)}")
+        if inplace:
+            if out is not None and out.data_ptr() != x.data_ptr():
+                raise ValueError("ContextAdd: inplace and out are exclusive")
+            out = x
+        elif out is None:
+            out = torch.empty_like(x)
+        if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("ContextAdd: out must match x in shape, dtype, device and be contiguous")
+        if (x.data_ptr() | out.data_ptr()) % 16:
+            raise ValueError("ContextAdd: x and out must be 16-byte aligned (the kernels load and store 16-byte vectors)")
+        n, s = int(x.shape[0]), int(x.numel() // (x.shape[0] * self.c))
+        lib = _lib.load()
+        # scratch only where the split route runs (route 0 picks from (s, c): fac_context_route), and from
+        # torch, like term: the caching allocator serves them under graph capture
+        scratch = None
+        if (int(route) or lib.fac_context_route(s, self.c)) == 2:
+            scratch = torch.empty(max(lib.fac_context_scratch_bytes(n, s, self.c) // 4, 1), dtype=torch.float32,
+                                  device=x.device)
+        term = torch.empty(n, self.c, dtype=torch.float32, device=x.device) if return_term else None
+        _lib.check(lib.fac_context_add(_lib.DTYPES[self.dtype_name], x.data_ptr(), n, s, self.c, self.p,
+                                       self.w0.data_ptr(), self.b0.data_ptr(), self.ln_w.data_ptr(),
+                                       self.ln_b.data_ptr(), self.eps, self.w3t.data_ptr(), self.b3.data_ptr(),
+                                       out.data_ptr(), term.data_ptr() if return_term else None,
+                                       scratch.data_ptr() if scratch is not None else None,
+                                       int(route), _stream(x)), None, "fac_context_add")
+        return (out, term) if return_term else out
+
+
 def sigmoid(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty_like(x)
     _lib.check(_lib.load().fac_sigmoid(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x)), None, "fac_sigmoid")

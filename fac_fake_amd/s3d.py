@@ -29,10 +29,11 @@ from torch import nn
 from . import _lib
 from .cvit import _Node, weight_versions
 from . import ops
-from .ops import TORCH16, ConvLayer, conv_split, fold_bn, max_pool_sep, pack_input, pack_input_s2d, pool, s2d_weight, sigmoid
+from .ops import TORCH16, ContextAdd, ConvLayer, conv_split, fold_bn, max_pool_sep, pack_input, pack_input_s2d, pool, s2d_weight, sigmoid
 from .weights import s3d_base, s3d_param_specs
 
 BN_EPS = 1e-3   # BatchNorm3d(eps=1e-3) in BasicConv3d / SepConv3d (model.py:54,67,71)
+LN_EPS = 1e-5   # nn.LayerNorm's default, the context blocks' (context_block_3d.py:34)
 _BUFFERS = ("rmean", "rvar", "nbt")
 
 
@@ -46,9 +47,9 @@ def _pad_rows(t: torch.Tensor, n: int) -> torch.Tensor:
 def _init_tensor(shape, kind):
     if kind == "nbt":
         return torch.zeros((), dtype=torch.long)
-    if kind in ("rmean", "beta", "lbias"):
+    if kind in ("rmean", "beta", "lbias", "ctx_b0", "ctx_lnb", "ctx_b3"):
         return torch.zeros(shape)
-    if kind in ("rvar", "gamma"):
+    if kind in ("rvar", "gamma", "ctx_lnw"):
         return torch.ones(shape)
     t = torch.empty(shape)
     bound = 1.0 / math.sqrt(int(math.prod(shape[1:])))
@@ -66,7 +67,7 @@ class S3D(nn.Module):
         self._srm = SRM_net == "yes"
         # base.0 of a uint8 16 x 112 x 112 clip as one launch (ops.s3d_base0_u8)
         self.fuse_base0 = True
-        for name, shape, kind in s3d_param_specs(num_class, self._srm):
+        for name, shape, kind in self._param_specs():
             *path, leaf = name.split(".")
             mod = self
             for p in path:
@@ -80,6 +81,14 @@ class S3D(nn.Module):
                 mod.register_parameter(leaf, nn.Parameter(t))
         self._prep = None
         self.eval()
+
+    # the layer descriptors of `base` and the state_dict layout: what a variant
+    # of the model with further layer kinds overrides (ca_s3d.CA_S3D_v3)
+    def _base_desc(self):
+        return s3d_base(self._srm)
+
+    def _param_specs(self):
+        return s3d_param_specs(self.num_class, self._srm)
 
     def _versions(self):
         return weight_versions(self)
@@ -130,9 +139,15 @@ class S3D(nn.Module):
             w = sd["SRM.hpf.weight"]
             self._srm_conv = ConvLayer(w, torch.zeros(w.shape[0]), 1, (0, 2, 2), dtype=dt, device=device)
         self._layers = []
-        for i, L in enumerate(s3d_base(self._srm)):
+        for i, L in enumerate(self._base_desc()):
             p = f"base.{i}"
-            if L[0] == "sep" and i == 0 and not self._srm:
+            if L[0] == "ctx":
+                # GCNet context block (ops.ContextAdd): global mean, Conv -> LayerNorm -> ReLU6 -> Conv, add
+                a = f"{p}.channel_add_conv"
+                self._layers.append(("ctx", ContextAdd(sd[a + ".0.weight"], sd[a + ".0.bias"], sd[a + ".1.weight"],
+                                                       sd[a + ".1.bias"], sd[a + ".3.weight"], sd[a + ".3.bias"],
+                                                       eps=LN_EPS, dtype=dt, device=device)))
+            elif L[0] == "sep" and i == 0 and not self._srm:
                 self._layers.append(("sep_s2d", sep_s2d(p)))
             elif L[0] == "sep":
                 self._layers.append(("sep", sep(p, L[3], L[4], L[5], cin_pad=32 if i == 0 else None)))
@@ -207,6 +222,8 @@ class S3D(nn.Module):
     # 8 x 14 x 14) as one launch (fac_sep_tiny / fac_sep_mid); False: the two
     # fac_conv_nd launches (A/B)
     fuse_sep = True
+    # route of the context blocks (fac_context_add): 0 auto, 1 per-clip, 2 split
+    ctx_route = 0
 
     def _pad64(self, c: int, level: int) -> int:
         if self.pad64_level < level or c % 64 == 0 or (level == 1 and c < 64):
@@ -293,6 +310,9 @@ class S3D(nn.Module):
                 y = L(y)
             elif kind == "pool":
                 y = max_pool_sep(y, *L)
+            elif kind == "ctx":
+                # in place on the Mixed block's output; a tap of that output keeps the pre-context tensor
+                y = L(y, inplace=taps is None, route=self.ctx_route)
             else:
                 y = self._mixed(y, L)
             if taps is not None:

@@ -318,10 +318,10 @@ def _s3d_sep(p, cin, cout, k):
             [(f"{p}.conv_t.weight", (cout, cout, k, 1, 1), "conv")] + _s3d_bn(f"{p}.bn_t", cout))
 
 
-def s3d_param_specs(num_class: int = 1, srm: bool = False):
-    """(name, shape, kind) for every key of S3D's state_dict, in its order."""
+def _s3d_family_specs(base, num_class):
+    """(name, shape, kind) for SRM, every entry of `base` and fc, in state_dict order."""
     specs = [("SRM.hpf.weight", (30, 3, 1, 5, 5), "srm")]
-    for i, L in enumerate(s3d_base(srm)):
+    for i, L in enumerate(base):
         p = f"base.{i}"
         if L[0] == "sep":
             specs += _s3d_sep(p, L[1], L[2], L[3])
@@ -333,8 +333,19 @@ def s3d_param_specs(num_class: int = 1, srm: bool = False):
             specs += _s3d_basic(f"{p}.branch1.0", cin, b1a) + _s3d_sep(f"{p}.branch1.1", b1a, b1b, 3)
             specs += _s3d_basic(f"{p}.branch2.0", cin, b2a) + _s3d_sep(f"{p}.branch2.1", b2a, b2b, 3)
             specs += _s3d_basic(f"{p}.branch3.1", cin, b3)
+        elif L[0] == "ctx":   # CA_S3D_v3's ContextBlock3d(C, 1/16, 'avg') (below)
+            c, q = L[1], L[2]
+            a = f"{p}.channel_add_conv"
+            specs += [(f"{a}.0.weight", (q, c, 1, 1, 1), "ctx_w0"), (f"{a}.0.bias", (q,), "ctx_b0"),
+                      (f"{a}.1.weight", (q, 1, 1, 1), "ctx_lnw"), (f"{a}.1.bias", (q, 1, 1, 1), "ctx_lnb"),
+                      (f"{a}.3.weight", (c, q, 1, 1, 1), "ctx_w3"), (f"{a}.3.bias", (c,), "ctx_b3")]
     specs += [("fc.0.weight", (num_class, 1024, 1, 1, 1), "fc"), ("fc.0.bias", (num_class,), "lbias")]
     return specs
+
+
+def s3d_param_specs(num_class: int = 1, srm: bool = False):
+    """(name, shape, kind) for every key of S3D's state_dict, in its order."""
+    return _s3d_family_specs(s3d_base(srm), num_class)
 
 
 def make_s3d_state_dict(seed: int = 0, num_class: int = 1, srm: bool = False) -> "OrderedDict[str, np.ndarray]":
@@ -368,6 +379,88 @@ def make_s3d_state_dict(seed: int = 0, num_class: int = 1, srm: bool = False) ->
             sd[name] = _u(name, shape, seed, 0.8, 1.0)
         else:
             sd[name] = _synthetic(name, shape, kind, seed)
+    return sd
+
+
+# ---------------------------------------------------------------- CA_S3D_v3
+# sx_exp_deepfakedetect-master/S3D/CA_S3D.py::CA_S3D_v3 (:9-60): S3D's `base`
+# with a GCNet ContextBlock3d(C, 1/16, pooling_type='avg')
+# (new_model/context_block_3d.py:5-88) after Mixed_3b, 4b, 4c, 4d, 4e and 5b:
+# 22 Sequential entries, the extra kind ("ctx", C, P) with P = int(C / 16).
+CA_S3D_CTX_AFTER = (5, 8, 9, 10, 11, 14)     # S3D base indices followed by a context block
+
+
+def ca_s3d_base(srm: bool):
+    """The `base` Sequential of CA_S3D_v3 (CA_S3D.py:20-46) as layer descriptors."""
+    out = []
+    for i, L in enumerate(s3d_base(srm)):
+        out.append(L)
+        if i in CA_S3D_CTX_AFTER:
+            c = L[2] + L[3][1] + L[4][1] + L[5]          # the Mixed block's concatenated width
+            out.append(("ctx", c, int(c * (1. / 16.))))
+    return out
+
+
+def _ca_s3d_name_map(srm: bool) -> dict:
+    """CA_S3D_v3 base index -> S3D base index of the same layer (context blocks absent)."""
+    m, j = {}, 0
+    for i, L in enumerate(ca_s3d_base(srm)):
+        if L[0] != "ctx":
+            m[i] = j
+            j += 1
+    return m
+
+
+def ca_s3d_param_specs(num_class: int = 1, srm: bool = False):
+    """(name, shape, kind) for every key of CA_S3D_v3's state_dict, in its order."""
+    return _s3d_family_specs(ca_s3d_base(srm), num_class)
+
+
+# Synthetic context-block weights.  LayerNorm makes the block blind to the
+# scale of W0 ctx + b0 and keeps only how the clips' pooled vectors differ, so
+# a careless choice gives every clip almost the same term.  b0 is small (it
+# would dilute those differences); the LayerNorm gain is 3..5 and its bias
+# -4..-2, so ReLU6 cuts about 0.75 sigma up, where a small shift of a value is
+# a large relative one (a later cut, 1.5 sigma, amplifies the 16-bit rounding
+# noise of the pooled vector just as much: the bf16 envelope then grows faster
+# than the clips' differences); W3 and b3 carry a gain per block (base index)
+# that puts the term's rms near the block's input rms, 0.8x .. 1.2x on the
+# fixture clips (1.4x at the last block), and b3 leans negative to slow the growth of the activations
+# that six added terms cause (they still reach about 1.7x, logits of 6 to 8).
+# tools/make_golden_ca_s3d.py asserts the outcome on the fixture clips.
+CA_S3D_CTX_GAIN = {6: 0.4, 10: 0.4, 12: 0.7, 14: 0.7, 16: 0.8, 20: 1.3}
+
+
+def make_ca_s3d_state_dict(seed: int = 0, num_class: int = 1, srm: bool = False) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic CA_S3D_v3 weights: every layer it shares with S3D has the
+    values make_s3d_state_dict gives that layer (same stream, keyed by the S3D
+    name); the context blocks draw from streams of their own names."""
+    s3d = make_s3d_state_dict(seed, num_class, srm)
+    nm = _ca_s3d_name_map(srm)
+    sd = OrderedDict()
+    for name, shape, kind in ca_s3d_param_specs(num_class, srm):
+        if not kind.startswith("ctx_"):
+            parts = name.split(".")
+            if parts[0] == "base":
+                parts[1] = str(nm[int(parts[1])])
+            sd[name] = s3d[".".join(parts)]
+            continue
+        blk = int(name.split(".")[1])
+        g = CA_S3D_CTX_GAIN[blk]
+        if kind == "ctx_w0":
+            a = float(np.sqrt(6.0 / shape[1]))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "ctx_b0":
+            sd[name] = _u(name, shape, seed, -0.002, 0.002)
+        elif kind == "ctx_lnw":
+            sd[name] = _u(name, shape, seed, 3.0, 5.0)
+        elif kind == "ctx_lnb":
+            sd[name] = _u(name, shape, seed, -4.0, -2.0)
+        elif kind == "ctx_w3":
+            a = float(g * np.sqrt(3.0 / shape[1]))
+            sd[name] = _u(name, shape, seed, -a, a)
+        else:
+            sd[name] = _u(name, shape, seed, -0.6 * g, 0.1 * g)
     return sd
 
 

@@ -261,6 +261,41 @@ size_t fac_kan_scratch_bytes(int rows, int in_f, int out_f);
 int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
              const float* bn4, const float* w2, const float* b2, void* out, void* stream);
 
+/* GCNet context block of CA_S3D_v3 — ContextBlock3d(c, ratio, pooling 'avg',
+ * fusion ('channel_add',)), sx_exp_deepfakedetect-master/S3D/new_model/
+ * context_block_3d.py:5-88 — on a 16-bit channels-last map x [n][s][c]
+ * (s = T*H*W positions per clip):
+ *   ctx[b][:]  = mean over s of x[b]                     (fp32 sum / s)
+ *   h          = w0 ctx[b] + b0                          (p values)
+ *   h          = LayerNorm over exactly those p values (biased variance,
+ *                ln_eps, affine ln_w / ln_b), then min(max(h, 0), 6)
+ *   term[b][:] = w3 h + b3                               (c values)
+ *   out        = round_to_nearest_even_16(float(x) + term[b][c])
+ * All of it fp32 between the 16-bit load and the one 16-bit conversion.
+ * w0 [p][c] (channel_add_conv.0.weight), b0 [p], ln_w / ln_b [p], b3 [c];
+ * w3t [p][c] is channel_add_conv.3.weight [c][p] TRANSPOSED (channel-minor,
+ * so a wavefront reads consecutive channels).  out may be x.  term, if not
+ * NULL, receives the fp32 [n][c] terms.  No atomics.
+ * route: 1 per-clip (one launch, one workgroup per clip; the clip is held in
+ * LDS when it fits), 2 split (partial sums over 64-row chunks, per-clip
+ * reduce + MLP, vectorised apply: three launches), 0 picks one from (s, c)
+ * alone (fac_context_route: per-clip for clips up to 256 KB).  Within one
+ * route a clip's term and output do not depend on n or on its place in the
+ * batch, and route 0 never switches with n, so the same holds for it; the
+ * two routes add the pool in different orders and may differ in the last
+ * bits of term.  scratch: fac_context_scratch_bytes(n, s, c) bytes of device
+ * memory (0 for a bad shape); needed by the split route only, so it may be
+ * NULL with route 1, or with route 0 when fac_context_route(s, c) is 1.
+ * x and out must be 16-byte aligned.
+ * FAC_ERR_SHAPE: c % 8 != 0, c > 4096, p < 1, p > 64, n < 1 or s < 1;
+ * FAC_ERR_ARG: a null or misaligned pointer, a bad dtype or route. */
+int fac_context_route(int s, int c);   /* 1 or 2: what route 0 takes; 0 for a bad shape */
+size_t fac_context_scratch_bytes(int n, int s, int c);
+int fac_context_add(int dtype, const void* x, int n, int s, int c, int p, const float* w0, const float* b0,
+                    const float* ln_w, const float* ln_b, float ln_eps, const float* w3t, const float* b3,
+                    void* out /* may == x */, float* term /* [n][c], may be NULL */, void* scratch,
+                    int route /* 0 auto, 1 per-clip, 2 split */, void* stream);
+
 /* The CViT conv-stack kernels as layers (fac_cvit.h runs them inside its
  * fused forward; the CViT variants of the reference stack them differently —
  * the RepBn8 variant, SURVEY §8f-4, whose DEConv blocks fold into plain 3x3
