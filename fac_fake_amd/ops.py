@@ -677,6 +677,188 @@ class ContextAdd:
         return (out, term) if return_term else out
 
 
+# ---------------------------------------------------------------- msca.hip
+class DWSepDesc(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int), ("inp", ctypes.c_void_p), ("ldi", ctypes.c_int), ("i_off", ctypes.c_int),
+                ("n", ctypes.c_int), ("t", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("c", ctypes.c_int),
+                ("kt", ctypes.c_int), ("k", ctypes.c_int), ("ws", ctypes.c_void_p), ("wt", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("act", ctypes.c_int),
+                ("scale2", ctypes.c_void_p), ("shift2", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("ldo", ctypes.c_int), ("o_off", ctypes.c_int), ("out_f32", ctypes.c_int)]
+
+
+DWSEP_ACTS = {"none": 0, "affine2": 1, "gelu": 2}
+EW_OPS = {"affine": 0, "gelu": 1, "mul": 2, "add": 3, "add_gelu": 4, "clamp6": 5, "add3": 6}
+
+
+def bn_affine(gamma, beta, mean, var, eps: float):
+    """Eval-mode BatchNorm as (scale, shift) fp32 on the host: scale = gamma / sqrt(var + eps)."""
+    f = lambda t: t.detach().to("cpu", torch.float32)  # noqa: E731
+    s = f(gamma) / torch.sqrt(f(var) + eps)
+    return s, f(beta) - f(mean) * s
+
+
+def _cl_slice(t: torch.Tensor, off: int, c: int, what: str, dtype=None):
+    """Checks that channels [off, off + c) of the contiguous channels-last
+    tensor t [..., ld] are a slice the msca.hip kernels take."""
+    if t.dim() < 2 or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"{what}: expected a contiguous channels-last GPU tensor, got {tuple(t.shape)}")
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{what}: expected {dtype}, got {t.dtype}")
+    ld = int(t.shape[-1])
+    if c < 8 or c % 8 or ld % 8 or off % 8 or off < 0 or off + c > ld:
+        raise ValueError(f"{what}: channels [{off}, {off + c}) of {ld} must be multiples of 8 inside the row")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{what}: must be 16-byte aligned (the kernels load and store 16-byte vectors)")
+    return ld
+
+
+class DWSepLayer:
+    """DWSepConv3d(c, (kt,k,k)) + its BatchNorm (given as scale / shift, see
+    bn_affine) + ReLU6 for fac_dwsep3d, then `act`: 'none', 'affine2' (a second
+    BatchNorm: scale2 / shift2) or 'gelu'.  w_s: conv_s.weight [c,1,1,k,k],
+    w_t: conv_t.weight [c,1,kt,1,1]; k in {3,5,7}, kt in {1,3} (kt = 1 is a
+    per-channel scale, folded into the spatial weights here)."""
+
+    def __init__(self, w_s, w_t, scale, shift, *, act: str = "none", scale2=None, shift2=None, dtype: str, device):
+        f = lambda t: t.detach().to("cpu", torch.float32)  # noqa: E731
+        w_s, w_t = f(w_s), f(w_t)
+        c = int(w_s.shape[0])
+        if w_s.dim() != 5 or tuple(w_s.shape[1:3]) != (1, 1) or w_s.shape[3] != w_s.shape[4]:
+            raise ValueError(f"DWSepLayer: conv_s.weight must be [c,1,1,k,k], got {tuple(w_s.shape)}")
+        k, kt = int(w_s.shape[3]), int(w_t.shape[2]) if w_t.dim() == 5 else -1
+        if tuple(w_t.shape) != (c, 1, kt, 1, 1):
+            raise ValueError(f"DWSepLayer: conv_t.weight must be [{c},1,kt,1,1], got {tuple(w_t.shape)}")
+        if k not in (3, 5, 7) or kt not in (1, 3):
+            raise ValueError(f"DWSepLayer: k must be 3, 5 or 7 and kt 1 or 3, got k={k} kt={kt}")
+        if c % 8:
+            raise ValueError(f"DWSepLayer: channels must be a multiple of 8, got {c}")
+        if act not in DWSEP_ACTS:
+            raise ValueError(f"DWSepLayer: act must be one of {list(DWSEP_ACTS)}")
+        if (act == "affine2") != (scale2 is not None and shift2 is not None):
+            raise ValueError("DWSepLayer: scale2 and shift2 go with act='affine2', and only with it")
+        if dtype not in _lib.DTYPES:
+            raise ValueError(f"dtype must be one of {list(_lib.DTYPES)}")
+        for v in (scale, shift, scale2, shift2):
+            if v is not None and f(v).numel() != c:
+                raise ValueError(f"DWSepLayer: per-channel tables must have {c} values")
+        ws = w_s.reshape(c, k * k)
+        if kt == 1:
+            ws = ws * w_t.reshape(c, 1)
+        self.c, self.k, self.kt, self.act, self.dtype = c, k, kt, act, dtype
+        self.ws = ws.t().contiguous().to(device)                       # tap-major [k*k][c]
+        self.wt = w_t.reshape(c, kt).t().contiguous().to(device) if kt == 3 else None
+        self.scale, self.shift = f(scale).reshape(c).contiguous().to(device), f(shift).reshape(c).contiguous().to(device)
+        self.scale2 = f(scale2).reshape(c).contiguous().to(device) if act == "affine2" else None
+        self.shift2 = f(shift2).reshape(c).contiguous().to(device) if act == "affine2" else None
+
+    def __call__(self, x: torch.Tensor, *, c_in_off: int = 0, out: torch.Tensor | None = None, c_off: int = 0,
+                 out_f32: bool = False) -> torch.Tensor:
+        if x.dim() != 5:
+            raise ValueError(f"DWSepLayer: expected [N,T,H,W,C], got {tuple(x.shape)}")
+        ldi = _cl_slice(x, c_in_off, self.c, "DWSepLayer input", TORCH16[self.dtype])
+        n, t, h, w, _ = x.shape
+        if out is None:
+            out = torch.empty(n, t, h, w, self.c, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+        if tuple(out.shape[:4]) != (n, t, h, w):
+            raise ValueError(f"DWSepLayer: out must be [{n},{t},{h},{w},C], got {tuple(out.shape)}")
+        ldo = _cl_slice(out, c_off, self.c, "DWSepLayer output", torch.float32 if out_f32 else x.dtype)
+        d = DWSepDesc()
+        d.dtype = _lib.DTYPES[self.dtype]
+        d.inp, d.ldi, d.i_off = x.data_ptr(), ldi, c_in_off
+        d.n, d.t, d.h, d.w, d.c, d.kt, d.k = n, t, h, w, self.c, self.kt, self.k
+        d.ws, d.wt = self.ws.data_ptr(), self.wt.data_ptr() if self.wt is not None else None
+        d.scale, d.shift, d.act = self.scale.data_ptr(), self.shift.data_ptr(), DWSEP_ACTS[self.act]
+        if self.act == "affine2":
+            d.scale2, d.shift2 = self.scale2.data_ptr(), self.shift2.data_ptr()
+        d.out, d.ldo, d.o_off, d.out_f32 = out.data_ptr(), ldo, c_off, int(out_f32)
+        _lib.check(_lib.load().fac_dwsep3d(ctypes.byref(d), _stream(x)), None, "fac_dwsep3d")
+        return out
+
+
+def ew(op: str, a: torch.Tensor, b: torch.Tensor | None = None, c3: torch.Tensor | None = None, *, c: int | None = None,
+       a_off: int = 0, b_off: int = 0, c3_off: int = 0, out: torch.Tensor | None = None, o_off: int = 0,
+       scale: torch.Tensor | None = None, shift: torch.Tensor | None = None) -> torch.Tensor:
+    """One fac_ew launch over channels-last 16-bit tensors: `op` of EW_OPS on
+    channels [a_off, a_off + c) of a (and of b, c3 at their offsets), written
+    to channels [o_off, o_off + c) of out (a new [..., c] tensor by default;
+    out may be a).  'affine' takes fp32 device tables scale, shift [c]."""
+    if op not in EW_OPS:
+        raise ValueError(f"ew: op must be one of {list(EW_OPS)}")
+    if a.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"ew: expected a 16-bit tensor, got {a.dtype}")
+    c = int(a.shape[-1]) - a_off if c is None else c
+    lda = _cl_slice(a, a_off, c, "ew a")
+    rows = a.numel() // lda
+    if out is None:
+        out = torch.empty(*a.shape[:-1], c, device=a.device, dtype=a.dtype)
+    ldo = _cl_slice(out, o_off, c, "ew out", a.dtype)
+    if out.numel() // ldo != rows:
+        raise ValueError("ew: out must have a's positions")
+    ptr, ld, off = [None, None], [0, 0], (b_off, c3_off)
+    need = {"mul": 1, "add": 1, "add_gelu": 1, "add3": 2}.get(op, 0)
+    for i, t in enumerate((b, c3)):
+        if (t is not None) != (i < need):
+            raise ValueError(f"ew: '{op}' takes {need} operand(s) besides a")
+        if t is not None:
+            ld[i] = _cl_slice(t, off[i], c, "ew operand", a.dtype)
+            if t.numel() // ld[i] != rows:
+                raise ValueError("ew: every operand must have a's positions")
+            ptr[i] = t.data_ptr()
+    if op == "affine":
+        for t in (scale, shift):
+            if t is None or t.dtype != torch.float32 or t.numel() != c or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"ew: 'affine' needs fp32 device tables scale, shift of {c} values")
+    _lib.check(_lib.load().fac_ew(0 if a.dtype == torch.bfloat16 else 1, EW_OPS[op], a.data_ptr(), lda, a_off,
+                                  ptr[0], ld[0], b_off, ptr[1], ld[1], c3_off,
+                                  scale.data_ptr() if op == "affine" else None,
+                                  shift.data_ptr() if op == "affine" else None, out.data_ptr(), ldo, o_off, rows, c,
+                                  _stream(a)), None, "fac_ew")
+    return out
+
+
+def clamp6_(x: torch.Tensor, c_off: int = 0, c: int | None = None) -> torch.Tensor:
+    """min(max(x, 0), 6) in place on channels [c_off, c_off + c) of x.  After a
+    conv's own ReLU and 16-bit rounding this gives the bits of one ReLU6
+    epilogue: 6 is a 16-bit value and the rounding is monotonic."""
+    return ew("clamp6", x, a_off=c_off, c=c, out=x, o_off=c_off)
+
+
+def msca_sum(a: torch.Tensor, dw5: DWSepLayer, dw7: DWSepLayer) -> torch.Tensor:
+    """The MSCA sum (msca_3d.py:55-63): (a + DWSep5(a)) + DWSep7(a).  Two
+    fac_dwsep3d launches and one fac_ew 'add3': each term is rounded to 16 bits
+    where it is stored, then the sum once."""
+    if dw5.k != 5 or dw7.k != 7 or dw5.c != dw7.c or dw5.act != "none" or dw7.act != "none":
+        raise ValueError("msca_sum: expected the 5- and 7-window DWSepLayers of one width, act 'none'")
+    return ew("add3", a, dw5(a), dw7(a))
+
+
+def bn_max_pool(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, kt: int, *, c_in_off: int = 0,
+                c: int | None = None, out: torch.Tensor | None = None, c_off: int = 0) -> torch.Tensor:
+    """MaxPool3d((kt,3,3), 1, (kt//2,1,1)) of x * scale + shift on channels
+    [c_in_off, c_in_off + c) of x [N,T,H,W,C] (fac_bn_maxpool3d): the iFormer
+    block's BatchNorm + pool branch read straight from the block input."""
+    if x.dim() != 5 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"bn_max_pool: expected a 16-bit [N,T,H,W,C] tensor, got {x.dtype} {tuple(x.shape)}")
+    if kt not in (1, 3):
+        raise ValueError(f"bn_max_pool: kt must be 1 or 3, got {kt}")
+    c = int(x.shape[-1]) - c_in_off if c is None else c
+    ldi = _cl_slice(x, c_in_off, c, "bn_max_pool input")
+    n, t, h, w, _ = x.shape
+    if out is None:
+        out = torch.empty(n, t, h, w, c, device=x.device, dtype=x.dtype)
+    if tuple(out.shape[:4]) != (n, t, h, w):
+        raise ValueError(f"bn_max_pool: out must be [{n},{t},{h},{w},C], got {tuple(out.shape)}")
+    ldo = _cl_slice(out, c_off, c, "bn_max_pool output", x.dtype)
+    for tb in (scale, shift):
+        if tb.dtype != torch.float32 or tb.numel() != c or not tb.is_cuda or not tb.is_contiguous():
+            raise ValueError(f"bn_max_pool: scale and shift must be fp32 device tables of {c} values")
+    _lib.check(_lib.load().fac_bn_maxpool3d(0 if x.dtype == torch.bfloat16 else 1, x.data_ptr(), ldi, c_in_off, n, t,
+                                            h, w, c, kt, scale.data_ptr(), shift.data_ptr(), out.data_ptr(), ldo,
+                                            c_off, _stream(x)), None, "fac_bn_maxpool3d")
+    return out
+
+
 def sigmoid(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty_like(x)
     _lib.check(_lib.load().fac_sigmoid(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x)), None, "fac_sigmoid")

@@ -120,11 +120,19 @@ class S3D(nn.Module):
                 w, b = _pad_rows(w, cout_pad), _pad_rows(b, cout_pad)
             return ConvLayer(w, b, stride, pad, dtype=dt, device=device, cin_pad=cin_pad)
 
-        def sep(p, k, s, pd, cin_pad=None, mid_pad=None):
+        def sep(p, k, s, pd, cin_pad=None, mid_pad=None, v2=False):
             # mid_pad: the (1,k,k) half's output (the (k,1,1) half's input)
-            # zero-padded to mid_pad channels
-            return (bconv(p, (1, s, s), (0, pd, pd), cin_pad, "s", cout_pad=mid_pad),
-                    bconv(p, (s, 1, 1), (pd, 0, 0), mid_pad, "t"))
+            # zero-padded to mid_pad channels.  v2 (SepConv3dV2, new_model/
+            # Conv3d.py:24-43): the (1,k,k) half has no BatchNorm and no
+            # activation (its caller runs it with relu=False)
+            if v2:
+                w = sd[p + ".conv_s.weight"].detach().float().cpu()
+                w = _pad_rows(w, mid_pad) if mid_pad else w
+                first = ConvLayer(w, torch.zeros(w.shape[0]), (1, s, s), (0, pd, pd), dtype=dt, device=device,
+                                  cin_pad=cin_pad)
+            else:
+                first = bconv(p, (1, s, s), (0, pd, pd), cin_pad, "s", cout_pad=mid_pad)
+            return (first, bconv(p, (s, 1, 1), (pd, 0, 0), mid_pad, "t"))
 
         def sep_s2d(p):
             # base.0 without SRM: the (1,7,7)/(1,2,2) 3-channel conv as a (1,4,4)/1 conv over
@@ -155,8 +163,12 @@ class S3D(nn.Module):
                 self._layers.append(("basic", bconv(p)))
             elif L[0] == "pool":
                 self._layers.append(("pool", L[1:]))
+            elif L[0] not in ("mixed", "mixed_v2"):
+                # a block kind of a variant of the model (msca_s3d.msca_S3D's iFormer blocks)
+                self._layers.append((L[0], self._prepare_block(p, L, sd, device)))
             else:
                 cin, b0, (b1a, b1b), (b2a, b2b), b3 = L[1:]
+                v2 = L[0] == "mixed_v2"   # SepConv3dV2 branches
                 # the three 1x1x1 heads reading the block input (branch0.0,
                 # branch1.0, branch2.0) also as ONE conv over their
                 # concatenated output channels (ops.conv_split)
@@ -181,10 +193,10 @@ class S3D(nn.Module):
                 # (convnd_pt with a partial column block). Mixed_3c, 384 clips:
                 # 327 -> 160 us (tools/archive/s3d_small_ab.py); 32 -> 64 is slower
                 m2w = (b2b + 127) // 128 * 128 if b2b > 64 and b2b % 64 else None
-                b1, b2 = sep(f"{p}.branch1.1", 3, 1, 1), sep(f"{p}.branch2.1", 3, 1, 1, mid_pad=m2w)
+                b1, b2 = sep(f"{p}.branch1.1", 3, 1, 1, v2=v2), sep(f"{p}.branch2.1", 3, 1, 1, mid_pad=m2w, v2=v2)
 
                 def padded(p=p, heads=heads, merged=merged, b1=b1, b2=b2, b1a=b1a, b1b=b1b, b2a=b2a, b2b=b2b,
-                           p1=p1, p2=p2, m1=m1, m2=m2):
+                           p1=p1, p2=p2, m1=m1, m2=m2, v2=v2):
                     # the channel-padded layers, built on the block's first
                     # forward below 14x14 (never for the larger
                     # blocks, whose padded copies no launch reads)
@@ -194,11 +206,11 @@ class S3D(nn.Module):
                         hb = [heads[0][1], _pad_rows(heads[1][1], p1), _pad_rows(heads[2][1], p2)]
                         merged_p = ConvLayer(torch.cat(hw), torch.cat(hb), 1, 0, dtype=dt, device=device)
                     return dict(
-                        b1p=b1 if (p1, m1) == (b1a, b1b) else sep(f"{p}.branch1.1", 3, 1, 1, cin_pad=p1, mid_pad=m1),
-                        b2p=b2 if (p2, m2) == (b2a, b2b) else sep(f"{p}.branch2.1", 3, 1, 1, cin_pad=p2, mid_pad=m2),
+                        b1p=b1 if (p1, m1) == (b1a, b1b) else sep(f"{p}.branch1.1", 3, 1, 1, cin_pad=p1, mid_pad=m1, v2=v2),
+                        b2p=b2 if (p2, m2) == (b2a, b2b) else sep(f"{p}.branch2.1", 3, 1, 1, cin_pad=p2, mid_pad=m2, v2=v2),
                         heads_p=merged_p)
                 self._layers.append(("mixed", dict(
-                    b1=b1, b2=b2, b3=bconv(f"{p}.branch3.1"), padded=padded,
+                    v2=v2, b1=b1, b2=b2, b3=bconv(f"{p}.branch3.1"), padded=padded,
                     heads=merged, head_splits=(b0, b0 + b1a), head_widths=(b1a, b2a),
                     head_splits_p=(b0, b0 + p1), head_widths_p=(p1, p2),
                     widths=(b0, b1b, b2b, b3))))
@@ -224,6 +236,21 @@ class S3D(nn.Module):
     fuse_sep = True
     # route of the context blocks (fac_context_add): 0 auto, 1 per-clip, 2 split
     ctx_route = 0
+    # every activation of the conv layers is ReLU6 (new_model/Conv3d.py, the
+    # msca_S3D family) instead of ReLU: each conv's own ReLU epilogue, then a 6-clamp
+    # in place (ops.clamp6_: the same bits as one ReLU6 epilogue).  The launches
+    # that fuse two convs with a ReLU between them (fac_s3d_base0_u8,
+    # fac_sep_tiny / fac_sep_mid) have no 6-clamp there and are not taken.
+    relu6 = False
+
+    def _c6(self, y):
+        return ops.clamp6_(y) if self.relu6 else y
+
+    def _prepare_block(self, p, L, sd, device):
+        raise NotImplementedError(f"{type(self).__name__} has no layer kind {L[0]!r}")
+
+    def _run_block(self, kind, L, y):
+        raise NotImplementedError(f"{type(self).__name__} has no layer kind {kind!r}")
 
     def _pad64(self, c: int, level: int) -> int:
         if self.pad64_level < level or c % 64 == 0 or (level == 1 and c < 64):
@@ -258,17 +285,19 @@ class S3D(nn.Module):
         h1 = torch.empty(n, d, h, w, hws[0], dtype=x.dtype, device=x.device)
         h2 = torch.empty(n, d, h, w, hws[1], dtype=x.dtype, device=x.device)
         conv_split(blk["heads" + sfx], x, blk["head_splits" + sfx], out, 0, h1, h2)
-        t1(s1(h1), out=out, c_off=o1)
-        if self.fuse_sep and (ops.sep_tiny_ok(s2, t2, h2) or ops.sep_mid_ok(s2, t2, h2)):
+        v2 = blk["v2"]                          # SepConv3dV2: nothing between the two halves
+        mid = (lambda y: y) if v2 else self._c6
+        t1(mid(s1(self._c6(h1), relu=not v2)), out=out, c_off=o1)
+        if self.fuse_sep and not self.relu6 and (ops.sep_tiny_ok(s2, t2, h2) or ops.sep_mid_ok(s2, t2, h2)):
             ops.sep_tiny(s2, t2, h2, out, o2)   # Mixed_3b's / 3c's branch2 SepConv in one launch
         else:
-            t2(s2(h2), out=out, c_off=o2)
+            t2(mid(s2(self._c6(h2), relu=not v2)), out=out, c_off=o2)
         b3 = blk["b3"]
         if self.fuse_pool3 and b3.maxpool3s1_ok(x, out, o3):
             b3(x, out=out, c_off=o3, maxpool3s1=True)       # pool + 1x1x1 in one launch (ops.hip maxpool3_pw)
         else:
             b3(max_pool_sep(x, 3, 1, 1), out=out, c_off=o3)
-        return out
+        return self._c6(out)                    # (relu6: all four slots at once)
 
     def features16(self, x16: torch.Tensor, taps: list | None = None) -> torch.Tensor:
         """`base` (model.py:17-33) on the packed clip (`_pack`: without SRM the
@@ -290,7 +319,7 @@ class S3D(nn.Module):
                     and taps is None and nxt[1].prepool3s2_ok(y)):   # (taps: base.1's own output is one)
                 # base.1's MaxPool3d((1,3,3),(1,2,2)) + base.2's 1x1x1 conv as one
                 # launch (FAC_CONV_PREPOOL3S2, ops.hip maxpool2s_pw)
-                y = nxt[1](y, prepool3s2=True)
+                y = self._c6(nxt[1](y, prepool3s2=True))
                 skip = True
                 continue
             if kind == "sep_s2d":
@@ -299,22 +328,25 @@ class S3D(nn.Module):
                 # cells (ops.pack_input_s2d) still take the plain conv.  A
                 # uint8 16 x 112 x 112 clip runs both halves as one launch
                 # (ops.s3d_base0_u8; fuse_base0 = False: the two launches)
-                if y.dtype == torch.uint8 and self.fuse_base0 and tuple(y.shape[2:]) == (16, 112, 112) and \
-                        _lib.exports("fac_s3d_base0_u8"):
+                if y.dtype == torch.uint8 and self.fuse_base0 and not self.relu6 and \
+                        tuple(y.shape[2:]) == (16, 112, 112) and _lib.exports("fac_s3d_base0_u8"):
                     y = ops.s3d_base0_u8(L[0], L[1], y)
                 else:
-                    y = L[1](ops.conv_s2d4_clip(L[0], y) if y.dtype in (torch.float32, torch.uint8) else L[0](y))
+                    y = self._c6(L[1](self._c6(ops.conv_s2d4_clip(L[0], y) if y.dtype in (torch.float32, torch.uint8)
+                                               else L[0](y))))
             elif kind == "sep":
-                y = L[1](L[0](y))
+                y = self._c6(L[1](self._c6(L[0](y))))
             elif kind == "basic":
-                y = L(y)
+                y = self._c6(L(y))
             elif kind == "pool":
                 y = max_pool_sep(y, *L)
             elif kind == "ctx":
                 # in place on the Mixed block's output; a tap of that output keeps the pre-context tensor
                 y = L(y, inplace=taps is None, route=self.ctx_route)
-            else:
+            elif kind == "mixed":
                 y = self._mixed(y, L)
+            else:
+                y = self._run_block(kind, L, y)
             if taps is not None:
                 taps.append(y)
         return y

@@ -464,6 +464,240 @@ def make_ca_s3d_state_dict(seed: int = 0, num_class: int = 1, srm: bool = False)
     return sd
 
 
+# ---------------------------------------------------------------- msca_S3D
+# sx_exp_deepfakedetect-master/S3D/msca_S3D.py::msca_S3D (:17-72): S3D's stem
+# and its last two Inception blocks (all with ReLU6, new_model/Conv3d.py)
+# around 11 iFormer blocks (new_model/iformer_3d.py).  Further kinds of `base`:
+#   ("iformer" | "iformer_light", C, low, kt)   low = make_divisible(C * ratio, 32)
+#   ("mixed_v2", cin, b0, (b1a, b1b), (b2a, b2b), b3)   SepConv3dV2 branches (no bn_s)
+MSCA_S3D_BLOCKS = ([("iformer_light", 192, 1 / 4, 1), ("iformer", 192, 1 / 4, 1)],
+                   [(k, 320, r, 3) for r in (1 / 3, 1 / 2, 2 / 3) for k in ("iformer_light", "iformer", "iformer")])
+
+
+def make_divisible(v, divisor=8, min_value=None, round_limit=.9):
+    """iformer_3d.py:10-16 (timm's): v rounded to a multiple of divisor, one
+    step up when rounding took off more than 10 %."""
+    min_value = min_value or divisor
+    new_v = max(min_value, int(v + divisor / 2) // divisor * divisor)
+    if new_v < round_limit * v:
+        new_v += divisor
+    return new_v
+
+
+def msca_s3d_base(srm: bool):
+    """The `base` Sequential of msca_S3D (msca_S3D.py:28-58) as layer descriptors (21 entries)."""
+    blk = lambda b: (b[0], b[1], make_divisible(b[1] * b[2], 32), b[3])  # noqa: E731
+    return ([("sep", 30 if srm else 3, 64, 7, 2, 3), ("pool",) + S3D_POOLS[1], ("basic", 64, 64),
+             ("sep", 64, 192, 3, 1, 1), ("pool",) + S3D_POOLS[4]] + [blk(b) for b in MSCA_S3D_BLOCKS[0]] +
+            [("basic", 192, 320), ("pool",) + S3D_POOLS[7]] + [blk(b) for b in MSCA_S3D_BLOCKS[1]] +
+            [("pool",) + S3D_POOLS[13], ("mixed_v2", 320, 192, (96, 208), (16, 48), 64), ("mixed", 512) + S3D_MIXED[15][1:]])
+
+
+def _dwsep_specs(p, c, kt, k):
+    return ([(f"{p}.conv_s.weight", (c, 1, 1, k, k), "dw_s"), (f"{p}.conv_t.weight", (c, 1, kt, 1, 1), "dw_t")] +
+            _s3d_bn(f"{p}.bn_t", c))
+
+
+def _conv_bias_specs(p, cin, cout, kind):
+    return [(f"{p}.weight", (cout, cin, 1, 1, 1), kind), (f"{p}.bias", (cout,), "lbias")]
+
+
+def _iformer_specs(p, c, low, kt, light):
+    h = (c - low) // 2
+    m, a = f"{p}.inceptionmixer", f"{p}.inceptionmixer.attn"
+    g = f"{a}.spatial_gating_unit"
+    specs = _s3d_bn(f"{p}.norm1", c)
+    specs += _s3d_basic(f"{m}.maxpool_fc.1", h, h) + _s3d_basic(f"{m}.fc_dw.0", h, h)
+    specs += _dwsep_specs(f"{m}.fc_dw.1", h, kt, 3) + _s3d_bn(f"{m}.fc_dw.2", h)
+    specs += _conv_bias_specs(f"{a}.proj_1", low, low, "proj_1")
+    specs += _dwsep_specs(f"{g}.conv0", low, kt, 3) + _dwsep_specs(f"{g}.conv0_1", low, kt, 5)
+    specs += _dwsep_specs(f"{g}.conv1_1", low, kt, 7)
+    specs += _conv_bias_specs(f"{g}.conv3", low, low, "conv3") + _conv_bias_specs(f"{a}.proj_2", low, low, "proj_2")
+    if not light:
+        specs += _s3d_bn(f"{p}.norm2", c)
+        specs += _conv_bias_specs(f"{p}.mlp.fc1", c, 4 * c, "proj_1")
+        specs += _dwsep_specs(f"{p}.mlp.dwconv.dwconv", 4 * c, 3, 3)
+        specs += _conv_bias_specs(f"{p}.mlp.fc2", 4 * c, c, "fc2")
+    return specs
+
+
+def _sep_v2_specs(p, cin, cout, k):
+    return ([(f"{p}.conv_s.weight", (cout, cin, 1, k, k), "conv_lin"), (f"{p}.conv_t.weight", (cout, cout, k, 1, 1), "conv")] +
+            _s3d_bn(f"{p}.bn_t", cout))
+
+
+def msca_s3d_param_specs(num_class: int = 1, srm: bool = False):
+    """(name, shape, kind) for every key of msca_S3D's state_dict, in its order (853 keys)."""
+    specs = [("SRM.hpf.weight", (30, 3, 1, 5, 5), "srm")]
+    for i, L in enumerate(msca_s3d_base(srm)):
+        p = f"base.{i}"
+        if L[0] == "sep":
+            specs += _s3d_sep(p, L[1], L[2], L[3])
+        elif L[0] == "basic":
+            specs += _s3d_basic(p, L[1], L[2])
+        elif L[0] in ("iformer", "iformer_light"):
+            specs += _iformer_specs(p, L[1], L[2], L[3], L[0] == "iformer_light")
+        elif L[0] in ("mixed", "mixed_v2"):
+            cin, b0, (b1a, b1b), (b2a, b2b), b3 = L[1:]
+            sep = _sep_v2_specs if L[0] == "mixed_v2" else _s3d_sep
+            specs += _s3d_basic(f"{p}.branch0.0", cin, b0)
+            specs += _s3d_basic(f"{p}.branch1.0", cin, b1a) + sep(f"{p}.branch1.1", b1a, b1b, 3)
+            specs += _s3d_basic(f"{p}.branch2.0", cin, b2a) + sep(f"{p}.branch2.1", b2a, b2b, 3)
+            specs += _s3d_basic(f"{p}.branch3.1", cin, b3)
+    specs += [("fc.0.weight", (num_class, 1024, 1, 1, 1), "fc"), ("fc.0.bias", (num_class,), "lbias")]
+    return specs
+
+
+# Synthetic msca_S3D weights.  ReLU6 only differs from ReLU where a
+# pre-activation exceeds 6, so every BatchNorm that feeds a ReLU6 gets gamma
+# 2.5..3.5 and beta 4..5 on a roughly standardised input: pre-activations near
+# N(4.5, 3^2), 10-42 % above 6 and 2 % or more below 0 on the fixture clips
+# (tools/make_golden_msca_s3d.py asserts it per site).  "Standardised" needs
+# running statistics that fit what the layer sees: MSCA_S3D_BN_CAL holds, per
+# BatchNorm (in state_dict order, per SRM setting), the mean and variance of
+# its input over the fixture clips, measured layer by layer with
+# tools/calibrate_msca_s3d.py on the project's own fp32 restatement (each
+# BatchNorm's statistics fixed before the next layer is measured); running_mean
+# and running_var are drawn around them.  The BatchNorms with no ReLU6 behind
+# them are calibrated the same way: norm1 and norm2 have unit gain; fc_dw.2
+# has gamma 1.5..2.5 and beta -2.5..-1.5, which (with a large proj_2) puts 12 %
+# and more of the light blocks' GELU inputs below 0.  The biased 1x1x1 convs
+# have no BatchNorm, so their ranges assume their input's mean square
+# (MSCA_S3D_IN_MS): 1 after a norm (proj_1, fc1), ~180 for the MSCA sum of
+# three ReLU6 maps (conv3), ~20 after ReLU6 (+ GELU) (fc2, SepConv3dV2's first
+# half), and a deliberately small 0.03 for the gated map, which makes proj_2's
+# output large.  The residual stream grows to an rms near 19 over the nine
+# 320-wide blocks; norm1 / norm2 are calibrated to it.
+MSCA_S3D_BN_CAL: dict = {
+    False: [
+        (40.8165, 14971.6), (0.157447, 16.6552), (0.341458, 22.7747), (-0.12263, 18.2467),
+        (0.0840179, 17.7816), (4.12813, 3.77076), (-0.0123501, 0.874439), (-0.0311633, 0.956866),
+        (1.13679, 138.78), (4.00315, 3.38102), (-0.0375026, 3.41967), (2.57762, 302.271),
+        (0.945463, 444.617), (5.13812, 12.3546), (0.0957654, 1.07555), (0.058869, 1.3521),
+        (0.0196743, 144.743), (4.03328, 3.2543), (0.269106, 1.6865), (-2.13116, 260.681),
+        (0.659311, 436.862), (5.73466, 32.4067), (0.0661357, 6.91907), (-0.639104, 65.2445),
+        (4.16892, 3.91677), (0.0368607, 1.03798), (-0.0738686, 0.761896), (-0.532174, 82.33),
+        (4.14923, 3.57966), (-0.093533, 2.28706), (-0.517318, 189.772), (-0.579874, 185.432),
+        (5.31541, 17.0182), (0.124523, 1.24961), (0.0667094, 0.953783), (0.542049, 103.181),
+        (4.05995, 2.95561), (0.0819247, 0.994174), (0.223342, 141.427), (1.19676, 175.186),
+        (6.0944, 45.5395), (-0.0995799, 5.23644), (6.1552, 45.8323), (0.0855029, 0.956435),
+        (-0.18226, 1.31487), (-0.784022, 92.7842), (4.0873, 3.18002), (-0.215556, 2.09548),
+        (-1.78335, 161.624), (-0.940089, 376.781), (6.67714, 84.9631), (-0.100613, 5.42647),
+        (6.6245, 86.6267), (0.039696, 0.631953), (-0.121402, 0.993459), (1.96108, 68.9676),
+        (4.08969, 2.73944), (-0.0420239, 2.20155), (0.280293, 197.152), (-0.549561, 245.501),
+        (8.43803, 73.2943), (-0.00185051, 0.537883), (-0.02378, 1.06344), (-0.308795, 73.7775),
+        (4.07646, 3.36876), (-0.0281922, 2.4937), (1.53395, 166.034), (0.316806, 233.859),
+        (8.73433, 111.268), (0.0205395, 5.00547), (8.66612, 112.225), (0.0189122, 0.724014),
+        (-0.0265333, 0.922399), (-0.215598, 93.5702), (4.0648, 2.99673), (-0.0468547, 1.61914),
+        (0.0391394, 154.177), (1.58007, 239.241), (9.27397, 151.602), (0.0661195, 5.02502),
+        (9.32919, 152.863), (-0.0279978, 0.334442), (-0.094238, 0.434485), (1.70933, 100.946),
+        (4.06381, 2.81324), (-0.0429425, 2.64754), (-0.0189791, 163.005), (0.262242, 239.292),
+        (11.3837, 132.375), (-0.025808, 0.642774), (0.0242975, 0.494684), (-0.95712, 150.048),
+        (4.19951, 3.50209), (0.120113, 3.03925), (0.111676, 155.941), (1.2946, 217.975),
+        (11.7875, 150.444), (0.0536401, 5.15989), (11.8268, 151.296), (0.0757195, 0.652151),
+        (-0.00767412, 0.766021), (-1.16957, 118.089), (4.24542, 3.7649), (-0.11815, 1.80419),
+        (-0.343815, 194.773), (-0.598603, 262.811), (12.1342, 176.923), (0.111, 5.60552),
+        (1.23193, 376.465), (-2.48059, 311.215), (-0.0401879, 0.40643), (-1.52931, 345.014),
+        (-0.0429225, 0.367395), (-1.21064, 373.037), (-0.146132, 20.4231), (-0.336169, 19.5325),
+        (-0.161093, 10.5518), (-0.108772, 14.2712), (-0.991817, 15.5723), (-0.018554, 11.6254),
+        (-0.157842, 12.1391), (-0.0923984, 25.1031),
+    ],
+    True: [
+        (-0.227465, 3267.9), (0.294401, 15.7935), (0.416239, 27.6913), (-0.0888654, 18.1593),
+        (0.0743606, 17.8184), (4.14638, 3.75721), (-0.0128761, 0.88061), (-0.0280651, 0.949901),
+        (1.15544, 138.836), (4.00765, 3.37433), (-0.0586472, 3.54064), (2.55536, 306.051),
+        (0.945019, 446.708), (5.15415, 12.4618), (0.0873094, 1.06086), (0.067246, 1.37308),
+        (0.00393243, 144.673), (4.03573, 3.26652), (0.258619, 1.66819), (-2.10501, 262.702),
+        (0.661628, 438.42), (5.75066, 32.6128), (0.0701477, 6.90778), (-0.631257, 65.5487),
+        (4.16868, 3.91804), (0.0362517, 1.04416), (-0.071852, 0.754995), (-0.531242, 82.4431),
+        (4.149, 3.5806), (-0.0960763, 2.29396), (-0.534471, 189.391), (-0.56768, 185.616),
+        (5.31685, 17.0574), (0.126286, 1.25674), (0.0661237, 0.954938), (0.542198, 102.759),
+        (4.05915, 2.95709), (0.080348, 0.997586), (0.229648, 141.753), (1.20365, 175.222),
+        (6.09602, 45.6023), (-0.0989817, 5.2379), (6.15675, 45.8879), (0.0851225, 0.95746),
+        (-0.181881, 1.31141), (-0.790159, 92.6227), (4.08758, 3.18447), (-0.216312, 2.09549),
+        (-1.77829, 161.84), (-0.937411, 377.037), (6.67888, 85.0476), (-0.0996607, 5.42528),
+        (6.62604, 86.7221), (0.0408476, 0.636213), (-0.120356, 0.98739), (1.96612, 68.9561),
+        (4.08906, 2.74074), (-0.0428251, 2.19374), (0.28306, 197.171), (-0.548472, 245.537),
+        (8.44402, 73.2789), (-0.000299949, 0.535985), (-0.021974, 1.05684), (-0.311197, 73.808),
+        (4.077, 3.36549), (-0.0283, 2.49821), (1.53129, 166.134), (0.318766, 233.825),
+        (8.74363, 111.157), (0.0201078, 5.01406), (8.67524, 112.092), (0.0198676, 0.722064),
+        (-0.0239945, 0.92206), (-0.213495, 93.9883), (4.06491, 2.99056), (-0.0453977, 1.63015),
+        (0.0397768, 153.854), (1.57694, 238.828), (9.28243, 151.499), (0.0668033, 5.02032),
+        (9.33757, 152.755), (-0.0274253, 0.3375), (-0.0947037, 0.430227), (1.70584, 101.112),
+        (4.06426, 2.81282), (-0.0436106, 2.66733), (-0.02307, 163.011), (0.260597, 239.238),
+        (11.3917, 132.294), (-0.0259853, 0.649756), (0.0240617, 0.494305), (-0.963163, 150.283),
+        (4.19857, 3.50183), (0.11965, 3.03579), (0.109917, 155.919), (1.29343, 217.887),
+        (11.7914, 150.449), (0.0542647, 5.14958), (11.8311, 151.3), (0.077235, 0.655066),
+        (-0.00879003, 0.764616), (-1.15765, 118.215), (4.24469, 3.7612), (-0.119429, 1.79996),
+        (-0.344584, 194.947), (-0.607081, 262.999), (12.141, 177.011), (0.111357, 5.59912),
+        (1.23774, 376.911), (-2.49313, 311.732), (-0.0404121, 0.406805), (-1.49786, 345.561),
+        (-0.0430546, 0.36678), (-1.22851, 373.285), (-0.146121, 20.4197), (-0.336174, 19.5336),
+        (-0.161123, 10.5515), (-0.108909, 14.2708), (-0.989859, 15.5707), (-0.0178615, 11.6224),
+        (-0.157732, 12.1392), (-0.0944681, 25.0769),
+    ],
+}
+MSCA_S3D_IN_MS = {"proj_1": 1.0, "conv3": 180.0, "proj_2": 0.03, "fc2": 20.0, "conv_lin": 20.0}
+
+
+def msca_s3d_bn_names(srm: bool) -> list:
+    """The BatchNorm prefixes of msca_S3D in state_dict order (122)."""
+    return [n[:-len(".running_mean")] for n, _, k in msca_s3d_param_specs(1, srm) if k == "rmean"]
+
+
+def msca_s3d_running(name: str, n: int, seed: int, m: float, v: float) -> np.ndarray:
+    """running_mean (m +- 0.2 sqrt(v)) or running_var (v x 0.8..1.2) of one BatchNorm, by the key's name."""
+    u = uniform(name, n, seed)
+    if name.endswith("running_mean"):
+        return (np.float32(m) + np.float32(0.2 * np.sqrt(v)) * u).astype(np.float32)
+    return (np.float32(v) * (np.float32(1.0) + np.float32(0.2) * u)).astype(np.float32)
+
+
+def make_msca_s3d_state_dict(seed: int = 0, num_class: int = 1, srm: bool = False, cal=None) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic msca_S3D weights (scheme above).  cal: {BatchNorm prefix:
+    (mean, var)} overriding MSCA_S3D_BN_CAL (the calibration tool's own use);
+    a BatchNorm without an entry gets mean 0, variance 1."""
+    if cal is None:
+        cal = dict(zip(msca_s3d_bn_names(srm), MSCA_S3D_BN_CAL[bool(srm)]))
+    sd = OrderedDict()
+    for name, shape, kind in msca_s3d_param_specs(num_class, srm):
+        bn = name.rsplit(".", 1)[0]
+        relu6_bn = not (bn.endswith(("norm1", "norm2", "fc_dw.2")))
+        if kind == "nbt":
+            sd[name] = np.array(0, dtype=np.int64)
+        elif kind in ("conv", "dw_t"):
+            a = float(np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "dw_s":
+            # both signs, but a positive sum per window: a depthwise conv whose taps sum to ~0 would
+            # hide a shift of its input's mean (plain ReLU for ReLU6 in front of it) from every later layer
+            a = float(np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[name] = _u(name, shape, seed, -0.5 * a, 1.5 * a)
+        elif kind in MSCA_S3D_IN_MS:
+            a = float(np.sqrt(3.0 / (int(np.prod(shape[1:])) * MSCA_S3D_IN_MS[kind])))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "srm":
+            w = _u(name, shape, seed, -0.25, 0.25)
+            sd[name] = (w - w.mean(axis=(3, 4), keepdims=True)).astype(np.float32)
+        elif kind == "fc":
+            a = float(1.0 / np.sqrt(shape[1]))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "lbias":
+            sd[name] = _u(name, shape, seed, -0.2, 0.2)
+        elif kind == "gamma":
+            lo, hi = (2.5, 3.5) if relu6_bn else (1.5, 2.5) if bn.endswith("fc_dw.2") else (0.8, 1.2)
+            sd[name] = _u(name, shape, seed, lo, hi)
+        elif kind == "beta":
+            lo, hi = (4.0, 5.0) if relu6_bn else (-2.5, -1.5) if bn.endswith("fc_dw.2") else (-0.2, 0.2)
+            sd[name] = _u(name, shape, seed, lo, hi)
+        elif kind == "rmean":
+            sd[name] = msca_s3d_running(name, shape[0], seed, *cal.get(bn, (0.0, 1.0)))
+        elif kind == "rvar":
+            sd[name] = msca_s3d_running(name, shape[0], seed, *cal.get(bn, (0.0, 1.0)))
+        else:  # pragma: no cover
+            raise ValueError(kind)
+    return sd
+
+
 def s3d_clips(n: int, frames: int, size: int, seed: int) -> np.ndarray:
     """n synthetic raw clips [n, 3, frames, size, size] float32 of integer pixel
     values 0..255 (S3D's un-normalised BGR input, S3D-test.py:94-96)."""

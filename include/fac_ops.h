@@ -296,6 +296,67 @@ int fac_context_add(int dtype, const void* x, int n, int s, int c, int p, const 
                     void* out /* may == x */, float* term /* [n][c], may be NULL */, void* scratch,
                     int route /* 0 auto, 1 per-clip, 2 split */, void* stream);
 
+/* The iFormer / MSCA blocks of msca_S3D (sx_exp_deepfakedetect-master/S3D/
+ * new_model/iformer_3d.py, msca_3d.py, Conv3d.py) — msca.hip.  Activations
+ * are 16-bit channels-last [n][t][h][w][ld]; every operand is a channel slice
+ * [off, off + c) of rows of ld elements (ld, off, c multiples of 8, 16-byte
+ * aligned base), so slices are read in place and results land in their slot
+ * of a wider tensor.  fp32 between the 16-bit load and the one 16-bit
+ * conversion; a clip's result does not depend on n.  Nothing is allocated or
+ * synchronised; every launch goes to `stream`.
+ * FAC_ERR_SHAPE: a bad n/t/h/w/c, k or kt; FAC_ERR_ARG: a null or misaligned
+ * pointer, a slice outside its row, a bad dtype, act or op.
+ *
+ * fac_dwsep3d: DWSepConv3d(c, (kt,k,k), padding (kt/2,k/2,k/2)) — depthwise
+ * (1,k,k) conv, then depthwise (kt,1,1) conv, zero padding, no bias — then
+ *   v = min(max(acc * scale + shift, 0), 6)            (folded BN, ReLU6)
+ *   act FAC_DWSEP_AFFINE2: v = v * scale2 + shift2     (fc_dw's own BN)
+ *   act FAC_DWSEP_GELU:    v = v/2 (1 + erf(v/sqrt 2)) (the Mlp)
+ * k in {3,5,7}, kt in {1,3}.  ws: fp32 TAP-MAJOR [k*k][c] (conv_s.weight
+ * [c][1][k][k] transposed, so 8 channels of a tap are one vector); wt: fp32
+ * [kt][c] (conv_t.weight transposed), NULL when kt == 1 (the host folds that
+ * scale into ws).  Maps smaller than the window are fine.  out_f32: out is
+ * fp32 [..][ldo] instead of 16-bit (tests: the value before the rounding). */
+#define FAC_DWSEP_NONE 0
+#define FAC_DWSEP_AFFINE2 1
+#define FAC_DWSEP_GELU 2
+typedef struct {
+  int dtype;
+  const void* in;
+  int ldi, i_off;
+  int n, t, h, w, c;
+  int kt, k;
+  const float* ws;
+  const float* wt;
+  const float* scale;
+  const float* shift;
+  int act;
+  const float* scale2;
+  const float* shift2;
+  void* out;
+  int ldo, o_off;
+  int out_f32;
+} fac_dwsep_desc;
+int fac_dwsep3d(const fac_dwsep_desc* desc, void* stream);
+
+/* MaxPool3d((kt,3,3), stride 1, padding (kt/2,1,1)) of in * scale + shift
+ * (a BatchNorm applied on load: it does not commute with the max where a
+ * scale is negative), kt in {1,3}; one 16-bit rounding of the max. */
+int fac_bn_maxpool3d(int dtype, const void* in, int ldi, int i_off, int n, int t, int h, int w, int c, int kt,
+                     const float* scale, const float* shift, void* out, int ldo, int o_off, void* stream);
+
+/* Element-wise steps over rows x c: out = op(a[, b[, c3]]).  out may be a. */
+#define FAC_EW_AFFINE 0    /* a * scale[c] + shift[c] */
+#define FAC_EW_GELU 1      /* exact-erf GELU(a) */
+#define FAC_EW_MUL 2       /* a * b */
+#define FAC_EW_ADD 3       /* a + b */
+#define FAC_EW_ADD_GELU 4  /* GELU(a + b) */
+#define FAC_EW_CLAMP6 5    /* min(max(a, 0), 6) */
+#define FAC_EW_ADD3 6      /* (a + b) + c3: the MSCA sum */
+int fac_ew(int dtype, int op, const void* a, int lda, int a_off, const void* b, int ldb, int b_off, const void* c3,
+           int ldc, int c_off, const float* scale, const float* shift, void* out, int ldo, int o_off, long long rows,
+           int c, void* stream);
+
 /* The CViT conv-stack kernels as layers (fac_cvit.h runs them inside its
  * fused forward; the CViT variants of the reference stack them differently —
  * the RepBn8 variant, SURVEY §8f-4, whose DEConv blocks fold into plain 3x3
