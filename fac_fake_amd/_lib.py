@@ -85,6 +85,10 @@ SIGNATURES = {
     "fac_sigmoid": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "fac_conv_nd_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "fac_conv_nd_route": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_int)]),
+    "fac_conv_nd_dual_route": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
+    "fac_pool_nd_route": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     "fac_conv3x3_packed_elems": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fac_conv3x3_pack": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                         ctypes.c_void_p]),

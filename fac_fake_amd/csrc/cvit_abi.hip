@@ -20,20 +20,12 @@
 
 #include "../../include/fac_cvit.h"
 #include "common.hpp"
+#include "ops_common.hpp"  // ops.hip's knob setters
 
 namespace fac {
 void set_conv_ring9(int v);
 int conv_block_n(int H, int cout);
-void set_nd_pt_wide(int v);
 void set_gemm_small(int max_m, int variant);
-void set_nd_occ3(int v);
-void set_pool_roll(int v);
-void set_pool_win(int v);
-void set_pool3_zg(int v);
-void set_pool_lds14(int v);
-void set_pw_res(int v);
-void set_tk_wreg(int v);
-void set_pool3_g(int v);
 void pack_conv3x3(int dtype, int H, int ci, int co, const float* w, uint16_t* out, int bn = 0);
 void pack_stem_conv1(int dtype, const float* w, uint16_t* out);
 hipError_t launch_conv3x3(int dtype, const uint16_t* in, const uint16_t* wpk, const float* bias, uint16_t* out,

@@ -30,6 +30,7 @@
 #include "common.hpp"
 #include "fac_cvit.h"
 #include "fac_ops.h"
+#include "ops_common.hpp"
 
 namespace fac {
 
@@ -3998,6 +3999,589 @@ __global__ __launch_bounds__(512, 1) void convnd_pt(ConvP p, ConvP q) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing zero stages landed before LDS is released
 }
 
+// ---- host helpers
+// compute units of the device current at the first call (256 where it cannot be asked)
+static int cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return ncu;
+}
+inline int launch_status() { return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP; }
+inline bool dtype_ok(int dtype) { return dtype == FAC_DTYPE_BF16 || dtype == FAC_DTYPE_F16; }
+
+// f(BF16{}) or f(F16{}); FAC_ERR_ARG for any other dtype, else the status of what f launched
+template <class F>
+inline int with_dtype(int dtype, F&& f) {
+  if (dtype == FAC_DTYPE_BF16) f(BF16{});
+  else if (dtype == FAC_DTYPE_F16) f(F16{});
+  else return FAC_ERR_ARG;
+  return launch_status();
+}
+
+// kernel 1x1x1, stride 1, no padding
+inline bool is_pointwise(const fac_conv_desc* d) {
+  return d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 && d->pd == 0 &&
+         d->ph == 0 && d->pw == 0;
+}
+inline int relu1(const fac_conv_desc* d) { return (d->flags & FAC_CONV_RELU) != 0; }
+inline int relu2(const fac_conv_desc* d) { return (d->flags & FAC_CONV_RELU2) != 0; }
+
+// two convs fused into one launch (s, then t, reading `in`): all there, one dtype, ReLU the only flag
+inline bool conv_pair_ok(const fac_conv_desc* s, const fac_conv_desc* t, const void* in) {
+  return s && t && in && s->weight && t->weight && t->out && s->dtype == t->dtype && dtype_ok(s->dtype) &&
+         !((s->flags | t->flags) & ~FAC_CONV_RELU);
+}
+
+// the packed weight's sizes (fac_conv_weight_layout): rows in 128s, K in 64s
+inline int cout_padded(int cout) { return (cout + 127) / 128 * 128; }
+inline int k_padded(int cin, int kd, int kh, int kw) { return (kd * kh * kw * cin + 63) / 64 * 64; }
+inline int k_padded(const fac_conv_desc* d) { return k_padded(d->cin, d->kd, d->kh, d->kw); }
+
+// positive sizes, channels in 8-element pieces
+inline bool conv_dims_ok(const fac_conv_desc* d) {
+  return d->cin > 0 && d->cin % 8 == 0 && d->cout > 0 && d->n > 0 && d->d > 0 && d->h > 0 && d->w > 0;
+}
+
+// sizes past the kernels' index widths (checked last, after the caller's own checks)
+inline bool conv_too_large(const fac_conv_desc* d) {
+  return (long long)d->n * d->od * d->oh * d->ow >= (1LL << 31) ||
+         (long long)d->n * d->d * d->h * d->w * d->cin >= (1LL << 40);
+}
+
+// The kernels' parameter block of a descriptor that passed conv_dims_ok (one
+// output; the caller sets the column segments); false for a bad window,
+// output dims other than the floor-mode ones (every gathered tap then stays
+// within the padded input) or a k_pad other than fac_conv_weight_layout's.
+inline bool conv_params(const fac_conv_desc* d, ConvP& p) {
+  if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || d->sd <= 0 || d->sh <= 0 || d->sw <= 0) return false;
+  if (d->pd < 0 || d->ph < 0 || d->pw < 0 || d->od <= 0 || d->oh <= 0 || d->ow <= 0) return false;
+  if (d->od != (d->d + 2 * d->pd - d->kd) / d->sd + 1 || d->oh != (d->h + 2 * d->ph - d->kh) / d->sh + 1 ||
+      d->ow != (d->w + 2 * d->pw - d->kw) / d->sw + 1)
+    return false;
+  const int k_pad = k_padded(d);
+  if (d->k_pad != k_pad) return false;
+  p = ConvP{};
+  p.in = (const uint16_t*)d->in, p.w = (const uint16_t*)d->weight, p.res = (const uint16_t*)d->residual;
+  p.bias = d->bias, p.out = d->out;
+  p.D = d->d, p.H = d->h, p.W = d->w, p.C8 = d->cin / 8;
+  p.Do = d->od, p.Ho = d->oh, p.Wo = d->ow, p.Cout = d->cout;
+  p.KD = d->kd, p.KH = d->kh, p.KW = d->kw;
+  p.SD = d->sd, p.SH = d->sh, p.SW = d->sw;
+  p.PD = d->pd, p.PH = d->ph, p.PW = d->pw;
+  p.Kp = k_pad, p.ksteps = k_pad / 64, p.ktot8 = d->kd * d->kh * d->kw * (d->cin / 8);
+  p.ldo = d->ldo, p.c_off = d->c_off, p.ldr = d->ldr, p.r_off = d->r_off, p.flags = d->flags;
+  p.vec_out = (d->ldo % 8 == 0 && d->c_off % 8 == 0) ? 1 : 0;
+  p.vec_res = (d->ldr % 8 == 0 && d->r_off % 8 == 0) ? 1 : 0;
+  p.M = (int)((long long)d->n * d->od * d->oh * d->ow);  // (conv_too_large: rejected before any use)
+  p.split1 = p.split2 = INT_MAX;
+  return true;
+}
+
+// ---- routes: one fac_conv_nd / fac_conv_nd_split call (the descriptor, the
+// column segments, split1 = split2 = INT_MAX: none, and what is derived)
+struct ConvReq {
+  const fac_conv_desc* d;
+  void *out1, *out2;
+  int ldo1, ldo2, split1, split2;
+  bool split;           // split1 < cout
+  int k_pad, cout_pad;  // fac_conv_weight_layout's; p and M as conv_params fills them
+  long long M;          // (maxpool2s_pw is tried before they are known and reads d only)
+  ConvP p;
+};
+struct DualReq {  // one fac_conv_nd_dual call (p, q: the ConvP of d, ds)
+  const fac_conv_desc *d, *ds;
+  ConvP p, q;
+};
+
+// A route with a flag is the only one of the descriptors that set it: FAC_ERR_ARG where `matches` fails.
+template <class Req>
+struct Route {
+  const char* name;
+  bool (*matches)(const Req&);
+  int (*launch)(const Req&, hipStream_t);
+  int flag;
+};
+// The first of `routes` that takes r; nullptr with status set if none does.
+template <class Req, size_t N>
+static const Route<Req>* first_route(const Route<Req> (&routes)[N], const Req& r, int flags, int& status) {
+  for (const Route<Req>& rt : routes) {
+    if (rt.flag && !(flags & rt.flag)) continue;
+    if (rt.matches(r)) return status = FAC_OK, &rt;
+    if (rt.flag) return status = FAC_ERR_ARG, nullptr;
+  }
+  return status = FAC_ERR_SHAPE, nullptr;
+}
+
+// ---- fac_pool_nd's routes
+struct PoolReq { const fac_pool_desc* d; long long total; };  // total: (output position, 8-channel piece) pairs
+
+// A launch of `nb` 256-thread blocks, `work` items in all; FAC_ERR_SHAPE when
+// the items do not index in 32 bits.
+template <class F>
+static int pool_launch(const fac_pool_desc* d, long long work, F&& f) {
+  if (work >= (1LL << 31)) return FAC_ERR_SHAPE;
+  return with_dtype(d->dtype, [&](auto t) { f(t, (int)work, (int)((work + 255) / 256)); });
+}
+
+// MaxPool3d(3, 1, 1)
+static bool is_maxpool3(const fac_pool_desc* d) {
+  return d->mode == 0 && d->kd == 3 && d->kh == 3 && d->kw == 3 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
+         d->pd == 1 && d->ph == 1 && d->pw == 1 && d->od == d->d && d->oh == d->h && d->ow == d->w;
+}
+
+// process-wide (fac_set_option "pool_lds14"): 1 (default) MaxPool3d(3,1,1) on
+// 14 x 14 maps with 64-multiple channels by maxpool3_lds14, 0 maxpool3_s1
+static int g_pool_lds14 = 1;
+void set_pool_lds14(int v) { g_pool_lds14 = v; }
+static bool maxpool3_lds14_matches(const PoolReq& r) {
+  return is_maxpool3(r.d) && g_pool_lds14 && r.d->h == 14 && r.d->w == 14 && r.d->c % 64 == 0 && r.d->ldo % 8 == 0;
+}
+static int maxpool3_lds14_launch(const PoolReq& r, hipStream_t st) {
+  return pool_launch(r.d, (long long)r.d->n * (r.d->c / 64),
+                     [&](auto t, int nwg, int) { maxpool3_lds14<decltype(t)><<<nwg, 256, 0, st>>>(*r.d); });
+}
+
+// process-wide (fac_set_option "pool_roll"): MaxPool3d(3,1,1) on 7-wide
+// maps by maxpool3_roll (1: every frame in one thread, k >= 2: k output
+// frames per thread), 0: maxpool3_s1 (A/B)
+static int g_pool_roll = 1;
+void set_pool_roll(int v) { g_pool_roll = v; }
+static bool maxpool3_roll_matches(const PoolReq& r) { return is_maxpool3(r.d) && g_pool_roll && r.d->w == 7; }
+static int maxpool3_roll_launch(const PoolReq& r, hipStream_t st) {
+  const fac_pool_desc* d = r.d;
+  const int zg = g_pool_roll == 1 ? d->d : std::min(g_pool_roll, d->d);
+  return pool_launch(d, (long long)d->n * ((d->d + zg - 1) / zg) * d->h * (d->c / 8), [&](auto t, int rows, int nb) {
+    maxpool3_roll<decltype(t), 7><<<nb, 256, 0, st>>>(*d, rows, zg);
+  });
+}
+
+// process-wide (fac_set_option "pool3_zg"): output frames per thread of
+// maxpool3_s1 (0: all, the default)
+static int g_pool3_zg = 0;
+void set_pool3_zg(int v) { g_pool3_zg = v; }
+static bool maxpool3_s1_matches(const PoolReq& r) { return is_maxpool3(r.d); }
+static int maxpool3_s1_launch(const PoolReq& r, hipStream_t st) {
+  const fac_pool_desc* d = r.d;
+  const int zg = g_pool3_zg > 0 ? std::min(g_pool3_zg, d->d) : d->d;
+  return pool_launch(d, (long long)d->n * ((d->d + zg - 1) / zg) * d->h * d->w * (d->c / 8),
+                     [&](auto t, int cols, int nb) { maxpool3_s1<decltype(t)><<<nb, 256, 0, st>>>(*d, cols, zg); });
+}
+
+// process-wide (fac_set_option "pool_win"): 1 (default) the strided max pools
+// with a compile-time window by pool_max_win, 0 pool_nd (A/B)
+static int g_pool_win = 1;
+void set_pool_win(int v) { g_pool_win = v; }
+static bool is_window(const fac_pool_desc* d, int kd, int kh, int kw) { return d->kd == kd && d->kh == kh && d->kw == kw; }
+// compile-time windows (branch-free taps) for the max pools of S3D / ResNet:
+// floor-mode output dims and padding below the window keep a valid tap in
+// every window (pool_nd takes anything else)
+static bool pool_max_win_matches(const PoolReq& r) {
+  const fac_pool_desc* d = r.d;
+  const bool floor_dims = d->od == (d->d + 2 * d->pd - d->kd) / d->sd + 1 &&
+                          d->oh == (d->h + 2 * d->ph - d->kh) / d->sh + 1 &&
+                          d->ow == (d->w + 2 * d->pw - d->kw) / d->sw + 1 && d->pd >= 0 && d->ph >= 0 &&
+                          d->pw >= 0 && d->pd < d->kd && d->ph < d->kh && d->pw < d->kw;
+  return d->mode == 0 && g_pool_win && floor_dims &&
+         (is_window(d, 1, 3, 3) || is_window(d, 3, 3, 3) || is_window(d, 2, 2, 2));
+}
+static int pool_max_win_launch(const PoolReq& r, hipStream_t st) {
+  const fac_pool_desc* d = r.d;
+  return pool_launch(d, r.total, [&](auto t, int total, int nb) {
+    using T = decltype(t);
+    if (is_window(d, 1, 3, 3)) pool_max_win<T, 1, 3, 3><<<nb, 256, 0, st>>>(*d, total);
+    else if (is_window(d, 3, 3, 3)) pool_max_win<T, 3, 3, 3><<<nb, 256, 0, st>>>(*d, total);
+    else pool_max_win<T, 2, 2, 2><<<nb, 256, 0, st>>>(*d, total);
+  });
+}
+
+static bool pool_nd_matches(const PoolReq&) { return true; }
+static int pool_nd_launch(const PoolReq& r, hipStream_t st) {
+  return pool_launch(r.d, r.total, [&](auto t, int total, int nb) {
+    pool_nd<decltype(t)><<<nb, 256, 0, st>>>(*r.d, total);
+  });
+}
+
+// The order is the precedence.
+static const Route<PoolReq> kPoolRoutes[] = {
+    {"maxpool3_lds14", maxpool3_lds14_matches, maxpool3_lds14_launch, 0},
+    {"maxpool3_roll", maxpool3_roll_matches, maxpool3_roll_launch, 0},
+    {"maxpool3_s1", maxpool3_s1_matches, maxpool3_s1_launch, 0},
+    {"pool_max_win", pool_max_win_matches, pool_max_win_launch, 0},
+    {"pool_nd", pool_nd_matches, pool_nd_launch, 0},
+};
+
+static const Route<PoolReq>* pool_route(PoolReq& r, int& status) {
+  const fac_pool_desc* d = r.d;
+  status = FAC_ERR_ARG;
+  if (!d || !d->in || !d->out || !dtype_ok(d->dtype)) return nullptr;
+  status = FAC_ERR_SHAPE;
+  if (d->c <= 0 || d->c % 8 || d->n <= 0 || d->od <= 0 || d->oh <= 0 || d->ow <= 0 || d->mode < 0 || d->mode > 1)
+    return nullptr;
+  if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || d->sd <= 0 || d->sh <= 0 || d->sw <= 0) return nullptr;
+  if (d->ldo % 8 || d->c_off % 8 || d->ldo < d->c_off + d->c) return nullptr;
+  r.total = (long long)d->n * d->od * d->oh * d->ow * (d->c / 8);
+  if (r.total >= (1LL << 31)) return nullptr;
+  return first_route(kPoolRoutes, r, 0, status);
+}
+
+// ---- fac_conv_nd's routes with kernels of their own
+
+// MaxPool3d((1,3,3), (1,2,2), (0,1,1)) over the input, then this 1x1x1
+// 64 -> 64 conv (S3D's base.1 + base.2, FAC_CONV_PREPOOL3S2)
+static bool maxpool2s_pw_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return !(d->flags & ~(FAC_CONV_RELU | FAC_CONV_PREPOOL3S2)) && !r.out1 && !r.out2 && is_pointwise(d) &&
+         d->cin == 64 && d->cout == 64 && d->w == 56 && d->k_pad == 64 && d->od == d->d &&
+         d->oh == (d->h - 1) / 2 + 1 && d->ow == 28 && d->ldo % 8 == 0 && d->c_off % 8 == 0 && d->ldo >= d->c_off + 64;
+}
+static int maxpool2s_pw_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  constexpr int RB = 4;
+  const int nunits = d->n * d->d * ((d->oh + RB - 1) / RB);
+  const int grid = (nunits + 7) / 8 * 8;
+  return with_dtype(d->dtype, [&](auto t) {
+    maxpool2s_pw<decltype(t), 28, RB><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight,
+                                                            d->bias, (uint16_t*)d->out, nunits, d->h, d->oh, d->ldo,
+                                                            d->c_off, relu1(d));
+  });
+}
+
+// process-wide (fac_set_option "pool3_g"): frames per maxpool3_pw unit on
+// 7 x 7 maps, 0 = default (2), else 1 / 2 / 4 (A/B)
+static int g_pool3_g = 0;
+void set_pool3_g(int v) { g_pool3_g = v; }
+
+// MaxPool3d(3, 1, 1) over the input, then this 1x1x1 conv (S3D's
+// Inception branch3, FAC_CONV_MAXPOOL3S1)
+static bool maxpool3_pw_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  const int S = d->h;
+  return !r.split && !(d->flags & ~(FAC_CONV_RELU | FAC_CONV_MAXPOOL3S1)) && is_pointwise(d) && d->w == S &&
+         (S == 14 || S == 7 || S == 3) && d->cout % 32 == 0 && d->ldo % 8 == 0 && d->c_off % 8 == 0;
+}
+template <class T, int NCT>
+static auto maxpool3_pw_kernel(int S, int G) {
+  return S == 14 ? maxpool3_pw<T, 14, 1, NCT>
+         : S == 7 ? (G == 4 ? maxpool3_pw<T, 7, 4, NCT> : G == 2 ? maxpool3_pw<T, 7, 2, NCT> : maxpool3_pw<T, 7, 1, NCT>)
+                  : (G == 2 ? maxpool3_pw<T, 3, 2, NCT> : maxpool3_pw<T, 3, 1, NCT>);
+}
+static int maxpool3_pw_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const int S = d->h;
+  // frames per unit at 7 x 7: 2 by default (98 positions; fac_set_option
+  // "pool3_g" 1 / 2 / 4 forces one where the clip allows), at 3 x 3: 2
+  const int g7 = g_pool3_g ? g_pool3_g : 2;
+  const int G = S == 14 ? 1 : (S == 7 ? (d->d % g7 == 0 ? g7 : (d->d % 2 == 0 ? 2 : 1)) : (d->d % 2 == 0 ? 2 : 1));
+  const int nunits = d->n * (d->d / G);
+  // 128 columns per workgroup where cout allows (the pooled image is built
+  // once per unit instead of once per 64-column block), else 64 / 32
+  const int nct = d->cout % 128 == 0 ? 4 : (d->cout % 64 == 0 ? 2 : 1);
+  const dim3 grid((nunits + 7) / 8 * 8, d->cout / (32 * nct));
+  return with_dtype(d->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto k = nct == 4 ? maxpool3_pw_kernel<T, 4>(S, G) : nct == 2 ? maxpool3_pw_kernel<T, 2>(S, G) : maxpool3_pw_kernel<T, 1>(S, G);
+    k<<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias, (uint16_t*)d->out, nunits,
+                            d->d, d->cin, r.k_pad, d->ldo, d->c_off, relu1(d));
+  });
+}
+
+// SepConv3d(cin, cout, 3) on n x 8 x 14 x 14 as sep_tiny / sep_mid take it:
+// s the spatial (1,3,3) half cin -> mid, t the temporal (3,1,1) half mid ->
+// cout into a channel slot of the block output
+static int sep_check(const fac_conv_desc* s, const fac_conv_desc* t, int cin, int mid, int cout, int* kps, int* kpt) {
+  if (!conv_pair_ok(s, t, s ? s->in : nullptr)) return FAC_ERR_ARG;
+  *kps = k_padded(s), *kpt = k_padded(t);
+  auto map = [](const fac_conv_desc* d) {
+    return d->sd == 1 && d->sh == 1 && d->sw == 1 && d->d == 8 && d->h == 14 && d->w == 14 && d->od == 8 &&
+           d->oh == 14 && d->ow == 14;
+  };
+  const bool sp = s->cin == cin && s->cout == mid && s->kd == 1 && s->kh == 3 && s->kw == 3 && s->pd == 0 &&
+                  s->ph == 1 && s->pw == 1 && map(s) && s->k_pad == *kps && s->n > 0;
+  const bool tp = t->cin == mid && t->cout == cout && t->kd == 3 && t->kh == 1 && t->kw == 1 && t->pd == 1 &&
+                  t->ph == 0 && t->pw == 0 && map(t) && t->n == s->n && t->k_pad == *kpt && t->ldo % 8 == 0 &&
+                  t->c_off % 8 == 0 && t->ldo >= t->c_off + cout;
+  return sp && tp ? FAC_OK : FAC_ERR_SHAPE;
+}
+
+// the 4x4/1 conv over 16-channel space-to-depth cells, cout 64, no padding
+static bool is_s2d4(const fac_conv_desc* d) {
+  return d->kd == 1 && d->kh == 4 && d->kw == 4 && d->sd == 1 && d->sh == 1 && d->sw == 1 && d->pd == 0 &&
+         d->ph == 0 && d->pw == 0 && d->cin == 16 && d->cout == 64;
+}
+// ... with a dense output of whole 8 x 28 boxes
+static bool is_s2d4_boxes(const fac_conv_desc* d) {
+  return is_s2d4(d) && d->oh % 8 == 0 && d->ow % 28 == 0 && d->ldo == 64 && d->c_off == 0;
+}
+
+// + MaxPool2d(3, 2, 1): only the space-to-depth first conv with ReLU
+// (ResNet-50's conv1 -> bn1 -> relu -> maxpool, FAC_CONV_MAXPOOL3S2)
+static bool conv_s2d4_mp_matches(const ConvReq& r) {
+  return !r.split && is_s2d4_boxes(r.d) && r.k_pad == 256 && r.d->flags == (FAC_CONV_RELU | FAC_CONV_MAXPOOL3S2);
+}
+static int conv_s2d4_mp_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const int nimg = d->n * d->od, hp = d->oh / 2, wp = d->ow / 2, nstrip = nimg * (wp / 14);
+  const int grid = std::min(nstrip, 2 * cu_count());  // two resident (74 KB of LDS each)
+  return with_dtype(d->dtype, [&](auto t) {
+    conv_s2d4_mp<decltype(t)><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
+                                                    (uint16_t*)d->out, nstrip, d->h, d->w, hp, wp, r.k_pad);
+  });
+}
+
+// the space-to-depth first conv alone (no residual, dense output)
+static bool conv_s2d4_matches(const ConvReq& r) {
+  return !r.split && is_s2d4_boxes(r.d) && r.k_pad == 256 && (r.d->flags & ~FAC_CONV_RELU) == 0;
+}
+
+// conv_s2d4 over `in`: IN = 0 the cells themselves, 1 / 2 an fp32 / uint8
+// clip of h x w frames (d->d of them per clip) the cells are made from
+template <int IN>
+static int launch_s2d4(const fac_conv_desc* d, const void* in, int h, int w, int pad_before, hipStream_t st) {
+  const int nimg = d->n * d->od, nbox = nimg * (d->oh / 8) * (d->ow / 28);
+  const int grid = std::min(nbox, 2 * cu_count());  // two resident (two halo buffers + weights: 56 KB each)
+  return with_dtype(d->dtype, [&](auto t) {
+    if constexpr (IN == 0)
+      conv_s2d4<decltype(t)><<<grid, 256, 0, st>>>(in, (const uint16_t*)d->weight, d->bias, (uint16_t*)d->out, nbox,
+                                                   d->h, d->w, d->oh, d->ow, 256, relu1(d));
+    else
+      conv_s2d4<decltype(t), IN><<<grid, 256, 0, st>>>(in, (const uint16_t*)d->weight, d->bias, (uint16_t*)d->out,
+                                                       nbox, d->h, d->w, d->oh, d->ow, 256, relu1(d), d->d, h, w,
+                                                       pad_before);
+  });
+}
+static int conv_s2d4_launch(const ConvReq& r, hipStream_t st) { return launch_s2d4<0>(r.d, r.d->in, 0, 0, 0, st); }
+
+// fac_conv_s2d4_clip / _u8: the conv fac_conv_nd would run on
+// fac_pack_input_s2d(clip)'s cells
+template <int IN>
+static int conv_s2d4_clip(const fac_conv_desc* d, const void* clip, int h, int w, int pad_before, void* stream) {
+  if (!d || !clip || !d->weight || !d->out || !dtype_ok(d->dtype)) return FAC_ERR_ARG;
+  if ((d->flags & ~FAC_CONV_RELU) != 0 || h <= 0 || w <= 0 || h % 2 || w % 2 || pad_before < 0 || d->n <= 0 ||
+      d->d <= 0)
+    return FAC_ERR_ARG;
+  if (!is_s2d4_boxes(d) || d->k_pad != 256 || d->od != d->d || d->oh != d->h - 3 || d->ow != d->w - 3 ||
+      d->h < h / 2 + pad_before || d->w < w / 2 + pad_before)
+    return FAC_ERR_SHAPE;
+  if ((long long)d->n * d->d * 3 * h * w >= (1LL << 40)) return FAC_ERR_SHAPE;
+  return launch_s2d4<IN>(d, clip, h, w, pad_before, (hipStream_t)stream);
+}
+
+// process-wide (fac_set_option "pw_res"): 1 (default) the K = 128 / 256
+// bottleneck conv3 + identity by pw_res, 0 by convnd_pt (A/B); 2 keeps pw_res
+// and routes pw_res2's and pw_dual2's layers back to convnd_pt
+static int g_pw_res = 1;
+void set_pw_res(int v) { g_pw_res = v; }
+
+// one persistent workgroup per CU in whole rows of ny column blocks
+static int pw_grid(int ny) { return std::max(ny, cu_count() / ny * ny); }
+
+// S3D's merged Inception heads at K = 192 / 256 (fac_conv_nd_split, 1x1,
+// relu(conv + b) into up to three column segments): pw_res PLAIN, 128-wide
+// column blocks over the zero-padded weight rows
+static bool pw_res_split_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return g_pw_res && r.split && is_pointwise(d) && !(d->flags & ~FAC_CONV_RELU) && r.k_pad == d->cin &&
+         (d->cin == 192 || d->cin == 256) && d->ldo % 8 == 0 && d->c_off % 8 == 0 && r.ldo1 % 8 == 0 &&
+         r.ldo2 % 8 == 0 && r.split1 % 8 == 0 && (r.split2 == INT_MAX || r.split2 % 8 == 0) && r.cout_pad % 128 == 0;
+}
+static int pw_res_split_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const int ny = r.cout_pad / 128, G = pw_grid(ny);
+  return with_dtype(d->dtype, [&](auto t) {
+    auto k = d->cin == 192 ? pw_res<decltype(t), 6, 128, 64, 2> : pw_res<decltype(t), 8, 128, 64, 2>;
+    k<<<G, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias, nullptr, (uint16_t*)d->out,
+                         (int)r.M, r.k_pad, d->ldo, d->c_off, 0, 0, ny, relu1(d), 0, nullptr, nullptr, nullptr, d->cout,
+                         (uint16_t*)r.out1, r.ldo1, r.split1, (uint16_t*)r.out2, r.ldo2, r.split2);
+  });
+}
+
+// conv3 + identity of a bottleneck, relu(relu(conv + b) + residual), all 16-byte aligned
+static bool is_conv3_identity(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return !r.split && is_pointwise(d) && (d->flags & FAC_CONV_RESID) &&
+         !(d->flags & ~(FAC_CONV_RELU | FAC_CONV_RESID | FAC_CONV_RELU2)) && r.k_pad == d->cin && d->ldo % 8 == 0 &&
+         d->c_off % 8 == 0 && d->ldr % 8 == 0 && d->r_off % 8 == 0;
+}
+
+// ... at K = 128 / 256 (ResNet-50 layer2 / layer3): pw_res
+static bool pw_res_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return g_pw_res && is_conv3_identity(r) &&
+         ((d->cin == 128 && d->cout % 256 == 0) || (d->cin == 256 && d->cout % 128 == 0));
+}
+static int pw_res_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const int bn = d->cin == 128 ? 256 : 128, ny = d->cout / bn, G = pw_grid(ny);
+  return with_dtype(d->dtype, [&](auto t) {
+    auto k = d->cin == 128 ? pw_res<decltype(t), 4, 256, 64> : pw_res<decltype(t), 8, 128, 64>;
+    k<<<G, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias, (const uint16_t*)d->residual,
+                         (uint16_t*)d->out, (int)r.M, r.k_pad, d->ldo, d->c_off, d->ldr, d->r_off, ny, relu1(d),
+                         relu2(d), nullptr, nullptr, nullptr, INT_MAX, nullptr, 0, INT_MAX, nullptr, 0, INT_MAX);
+  });
+}
+
+// ... at K 512, cout % 256 == 0 (layer4): pw_res2, weights in VGPRs
+// ("pw_res" 2 routes it back to convnd_pt for A/B)
+static bool pw_res2_matches(const ConvReq& r) {
+  return g_pw_res == 1 && is_conv3_identity(r) && r.d->cin == 512 && r.d->cout % 256 == 0;
+}
+static int pw_res2_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const int ny = d->cout / 256, G = pw_grid(ny);
+  return with_dtype(d->dtype, [&](auto t) {
+    pw_res2<decltype(t)><<<G, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
+                                            (const uint16_t*)d->residual, (uint16_t*)d->out, (int)r.M, r.k_pad,
+                                            d->ldo, d->c_off, d->ldr, d->r_off, ny, relu1(d), relu2(d));
+  });
+}
+
+// stride-1 1x1 convs with K = cin in {64, 128, 256}: conv_pw
+// K 128 / 256 1x1s with cout % 128 == 0 go to convnd_pt instead: config 5
+// +1.2 % same-box (layer3's 256 -> 1024 + residual 160 -> 145 us)
+static bool conv_pw_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  const bool to_pt = (d->cin == 128 || d->cin == 256) && d->cout % 128 == 0;
+  return !r.split && !to_pt && is_pointwise(d) && (d->cin == 64 || d->cin == 128 || d->cin == 256) &&
+         r.k_pad == d->cin && d->cout % 64 == 0 && d->ldo % 8 == 0 && d->c_off % 8 == 0 &&
+         !(d->flags & FAC_CONV_OUT_F32) &&
+         (!(d->flags & FAC_CONV_RESID) || (d->ldr % 8 == 0 && d->r_off % 8 == 0));
+}
+static int conv_pw_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const bool res = d->flags & FAC_CONV_RESID;
+  const int ny = d->cout / 64;
+  // rows per tile and the LDS-bound residency: weights 64 x cin, two A
+  // buffers of bm x cin (+ two residual blocks of bm x 64), 160 KB per CU
+  const int bm = d->cin == 64 ? 128 : 64;
+  const int lds = 128 * d->cin + 4 * bm * d->cin + (res ? 256 * bm : 0);
+  const int occ = std::min(3, 163840 / lds);
+  const int ntiles = (int)((r.M + bm - 1) / bm);
+  // one persistent workgroup per resident slot over all column blocks, a
+  // multiple of 8 row slots so a row tile's column blocks share an XCD
+  const int gx = std::min(std::max(8, (occ * cu_count() / ny) / 8 * 8), ntiles);
+  const dim3 grid(gx, ny);
+  return with_dtype(d->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto k = d->cin == 64    ? (res ? conv_pw<T, 2, 2, true> : conv_pw<T, 2, 2, false>)
+             : d->cin == 128 ? (res ? conv_pw<T, 4, 1, true> : conv_pw<T, 4, 1, false>)
+                             : (res ? conv_pw<T, 8, 1, true> : conv_pw<T, 8, 1, false>);
+    k<<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias, (const uint16_t*)d->residual,
+                            (uint16_t*)d->out, (int)r.M, r.k_pad, d->ldo, d->c_off, d->ldr, d->r_off, d->flags);
+  });
+}
+
+// ---- fac_conv_nd_dual's routes
+
+// layer1's first block (64 -> 256 twice, the downsample at stride 1 over
+// the same positions): pw_res DUAL
+static bool pw_res_dual_matches(const DualReq& r) {
+  const fac_conv_desc *d = r.d, *ds = r.ds;
+  return g_pw_res && d->cin == 64 && ds->cin == 64 && d->cout % 256 == 0 && is_pointwise(d) && is_pointwise(ds) &&
+         r.p.Kp == 64 && r.q.Kp == 64;
+}
+static int pw_res_dual_launch(const DualReq& r, hipStream_t st) {
+  const ConvP &p = r.p, &q = r.q;
+  const int ny = p.Cout / 256, G = pw_grid(ny);
+  return with_dtype(r.d->dtype, [&](auto t) {
+    pw_res<decltype(t), 2, 256, 128, 1><<<G, 512, 0, st>>>(
+        p.in, p.w, p.bias, nullptr, (uint16_t*)p.out, p.M, 64, p.ldo, p.c_off, 0, 0, ny, relu1(r.d), relu2(r.d), q.in,
+        q.w, q.bias, INT_MAX, nullptr, 0, INT_MAX, nullptr, 0, INT_MAX);
+  });
+}
+
+// layer2's first block (conv3 128 -> 512 at 28^2, the downsample 256 -> 512
+// at stride 2 over the 56^2 block input) and layer3's: pw_dual2
+static bool pw_dual2_matches(const DualReq& r) {
+  const fac_conv_desc *d = r.d, *ds = r.ds;
+  return g_pw_res == 1 && ((d->cin == 128 && ds->cin == 256) || (d->cin == 256 && ds->cin == 512)) &&
+         d->cout % PWD2_BN == 0 && is_pointwise(d) && ds->kd == 1 && ds->kh == 1 && ds->kw == 1 && ds->sd == 1 &&
+         ds->sh == ds->sw && ds->pd == 0 && ds->ph == 0 && ds->pw == 0 && r.p.Kp == d->cin && r.q.Kp == ds->cin &&
+         d->d == 1 && ds->d == 1 && (long long)ds->h * ds->w * d->n < (1LL << 31);  // (x positions as int)
+}
+static int pw_dual2_launch(const DualReq& r, hipStream_t st) {
+  const ConvP &p = r.p, &q = r.q;
+  const int ny = p.Cout / PWD2_BN, G = pw_grid(ny);
+  return with_dtype(r.d->dtype, [&](auto t) {
+    auto k = r.d->cin == 128 ? pw_dual2<decltype(t), 128, 256, 64> : pw_dual2<decltype(t), 256, 512, 32>;
+    k<<<G, 512, 0, st>>>(p.in, p.w, p.bias, q.in, q.w, q.bias, (uint16_t*)p.out, p.M, r.d->cin, r.ds->cin, p.ldo,
+                         p.c_off, ny, p.Ho, p.Wo, q.H, q.W, q.SH, relu1(r.d), relu2(r.d));
+  });
+}
+
+static int g_tk_wreg = 1;  // conv_tk2 with the weights in VGPRs (cin 128 / 192)
+void set_tk_wreg(int v) { g_tk_wreg = v; }
+
+// S3D's temporal (kd,1,1) convs with 8 output frames, 64-multiple channels
+static bool is_temporal(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return !r.split && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && d->od == 8 &&
+         d->cin % 64 == 0 && d->cout % 64 == 0 && d->ldo % 4 == 0 && d->c_off % 4 == 0 &&
+         (d->flags & ~FAC_CONV_RELU) == 0 && r.k_pad == d->kd * d->cin;
+}
+static int tk_ksteps(const fac_conv_desc* d) { return d->kd * d->cin / 32; }  // K steps of 32 channels
+// conv_tk2's slices of KC 32-channel chunks (every chunk of a unit in one or
+// two steps: fewer per-step barriers and slice issues per MFMA), 3 ring slots
+static int tk2_kc(const fac_conv_desc* d) { return d->cin == 192 ? 3 : (d->cin == 128 ? 4 : 2); }
+
+// unit slots (a unit: 16 positions of a clip, the last one partial when 16
+// does not divide h*w): a multiple of 8 (slot = 8 * hi + lo, see conv_tk), at
+// most one per CU and per unit; x the column blocks of 64 channels
+struct TkGrid { int nunits, nbk, nslot; };
+static TkGrid tk_grid(const fac_conv_desc* d) {
+  const int nunits = d->n * ((d->h * d->w + 15) / 16);
+  return {nunits, d->cout / 64, (std::min(nunits, cu_count()) + 7) / 8 * 8};
+}
+
+// the (3,1,1) convs over 8 frames and the (7,1,1)/2 one over 16, cin 64 / 128
+// / 192, whose weights and 3-slot slice ring fit LDS: conv_tk2
+// (d->cin >= 64, i.e. >= 2 slices per unit and so at most R/2 store batches
+// per wait window, is implied by the cin set)
+static bool conv_tk2_matches(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  const bool k3 = d->kd == 3 && d->sd == 1 && d->pd == 1 && d->d == 8;
+  const bool k7 = d->kd == 7 && d->sd == 2 && d->pd == 3 && d->d == 16;
+  return is_temporal(r) && (k3 || k7) && (d->cin == 64 || d->cin == 128 || d->cin == 192) &&
+         tk_ksteps(d) * 2048 + 128 + 3 * tk2_kc(d) * d->d * 512 <= 81920 && d->cin >= 64;
+}
+static int conv_tk2_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const TkGrid g = tk_grid(d);
+  const int kc = tk2_kc(d);
+  return with_dtype(d->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto k = d->kd == 7 ? conv_tk2<T, 2, 7, 2, 2, 3>
+             : kc == 3  ? (g_tk_wreg ? conv_tk2<T, 1, 3, 1, 6, 3, 6> : conv_tk2<T, 1, 3, 1, 3, 3>)
+             : kc == 4  ? (g_tk_wreg ? conv_tk2<T, 1, 3, 1, 4, 3, 4> : conv_tk2<T, 1, 3, 1, 4, 3>)
+                        : conv_tk2<T, 1, 3, 1, 2, 3>;
+    k<<<dim3(g.nslot * g.nbk), 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
+                                             (uint16_t*)d->out, g.nunits, d->h * d->w, d->cin, r.k_pad, d->ldo,
+                                             d->c_off, relu1(d), g.nbk, g.nslot);
+  });
+}
+
+// any other temporal conv whose weights and one input slab (db 1) or two
+// (db 2) fit LDS: conv_tk
+static int tk_slabs(const fac_conv_desc* d) {
+  const int ks = tk_ksteps(d), slab = d->d * 16 * d->cin;
+  return ks * 2048 + 2 * slab <= 81920 ? 2 : (ks * 2048 + slab <= 81920 ? 1 : 0);
+}
+static bool conv_tk_matches(const ConvReq& r) { return is_temporal(r) && tk_slabs(r.d) != 0; }
+static int conv_tk_launch(const ConvReq& r, hipStream_t st) {
+  const fac_conv_desc* d = r.d;
+  const TkGrid g = tk_grid(d);
+  return with_dtype(d->dtype, [&](auto t) {
+    conv_tk<decltype(t)><<<dim3(g.nslot * g.nbk), 512, 0, st>>>(
+        (const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias, (uint16_t*)d->out, g.nunits, d->h * d->w, d->d,
+        d->cin, d->kd, d->sd, d->pd, r.k_pad, d->ldo, d->c_off, relu1(d), tk_slabs(d), g.nbk, g.nslot);
+  });
+}
+
+// ---- the generic conv's routes, then the dispatchers of fac_conv_nd / _split / _dual
+
 // grid of gx row tiles x ny column tiles: flat (column tiles of a row tile
 // adjacent, see convnd_igemm) unless it would overflow
 static dim3 conv_grid(ConvP& p, int gx, int ny) {
@@ -4014,110 +4598,177 @@ static dim3 conv_grid(ConvP& p, int gx, int ny) {
 // on; 0 keeps those on convnd_igemm (A/B)
 static int g_nd_pt_wide = 32;
 void set_nd_pt_wide(int v) { g_nd_pt_wide = v; }
+
+// convnd_pt's persistent grid over bn-wide column blocks: whole rows of
+// column blocks, at most one workgroup per CU and per tile
+static int convnd_pt_grid(const ConvP& p, int bn) {
+  const int nrt = (p.M + 255) / 256, ny = (p.Cout + bn - 1) / bn;
+  int G = cu_count() / ny * ny;
+  if ((long long)nrt * ny < G) G = nrt * ny;
+  return G;
+}
+static int convnd_pt_bn(const ConvP& p) { return (p.flags & FAC_CONV_RESID) ? 128 : (p.Cout % 256 == 0 ? 256 : 128); }
+
+// uniform-tap convs (cin % 64) of two K steps or more with a 16-byte-aligned
+// 16-bit output
+static bool convnd_pt_matches(const ConvReq& r) {
+  const ConvP& p = r.p;
+  const bool res = p.flags & FAC_CONV_RESID;
+  if (p.C8 % 8 || p.ksteps < 2 || !p.vec_out || p.Cout % 8 || (r.split && res) ||
+      (p.flags & FAC_CONV_OUT_F32) || (!res && (p.flags & FAC_CONV_RELU2)) || (res && !p.vec_res))
+    return false;
+  // a partial column block or column segments (fac_conv_nd_split): no
+  // residual tile, and enough row tiles that every persistent workgroup
+  // walks several (small late-block grids keep convnd_igemm's tiles)
+  if ((p.Cout % 128 || r.split) && (!g_nd_pt_wide || res || (p.M + 255) / 256 < g_nd_pt_wide)) return false;
+  return convnd_pt_grid(p, convnd_pt_bn(p)) > 0;
+}
+static int convnd_pt_launch(const ConvReq& r, hipStream_t st) {
+  ConvP p = r.p;
+  const bool res = p.flags & FAC_CONV_RESID;
+  const int bn = convnd_pt_bn(p), G = convnd_pt_grid(p, bn);
+  p.ny = 0;
+  return with_dtype(r.d->dtype, [&](auto t) {
+    using T = decltype(t);
+    if (res) convnd_pt<T, 128, true><<<G, 512, 0, st>>>(p, p);
+    else if (bn == 256) convnd_pt<T, 256><<<G, 512, 0, st>>>(p, p);
+    else convnd_pt<T, 128><<<G, 512, 0, st>>>(p, p);
+  });
+}
+
 // process-wide (fac_set_option "nd_occ3"): convnd_igemm's 3-per-CU 2-slot
 // 128 x 64 tile also for cout <= 64 up to this many K steps (default 4: S3D's
 // narrow SepConv halves, config 4 +0.3 to +0.6 %; 0: K <= 128 only)
 static int g_nd_occ3 = 4;
 void set_nd_occ3(int v) { g_nd_occ3 = v; }
-// process-wide (fac_set_option "pool_roll"): MaxPool3d(3,1,1) on 7-wide
-// maps by maxpool3_roll (1: every frame in one thread, k >= 2: k output
-// frames per thread), 0: maxpool3_s1 (A/B)
-static int g_pool_roll = 1;
-void set_pool_roll(int v) { g_pool_roll = v; }
-// process-wide (fac_set_option "pool_win"): 1 (default) the strided max pools
-// with a compile-time window by pool_max_win, 0 pool_nd (A/B)
-static int g_pool_win = 1;
-void set_pool_win(int v) { g_pool_win = v; }
-// process-wide (fac_set_option "pool3_zg"): output frames per thread of
-// maxpool3_s1 (0: all, the default)
-static int g_pool3_zg = 0;
-void set_pool3_zg(int v) { g_pool3_zg = v; }
-// process-wide (fac_set_option "pool_lds14"): 1 (default) MaxPool3d(3,1,1) on
-// 14 x 14 maps with 64-multiple channels by maxpool3_lds14, 0 maxpool3_s1
-static int g_pool_lds14 = 1;
-// process-wide (fac_set_option "pw_res"): 1 (default) the K = 128 / 256
-// bottleneck conv3 + identity by pw_res, 0 by convnd_pt (A/B)
-static int g_pw_res = 1;
-static int g_tk_wreg = 1;  // conv_tk2 with the weights in VGPRs (cin 128 / 192)
-// process-wide (fac_set_option "pool3_g"): frames per maxpool3_pw unit on
-// 7 x 7 maps, 0 = default (2), else 1 / 2 / 4 (A/B)
-static int g_pool3_g = 0;
-void set_pool3_g(int v) { g_pool3_g = v; }
-void set_pw_res(int v) { g_pw_res = v; }
-void set_tk_wreg(int v) { g_tk_wreg = v; }
-void set_pool_lds14(int v) { g_pool_lds14 = v; }
 
-template <class T>
-static bool launch_convnd_pt(ConvP& p, hipStream_t st) {
-  const bool res = p.flags & FAC_CONV_RESID;
-  const bool split = p.split1 < p.Cout;
-  if (p.ksteps < 2 || !p.vec_out || p.Cout % 8 || (split && res) ||
-      (p.flags & FAC_CONV_OUT_F32) || (!res && (p.flags & FAC_CONV_RELU2)) || (res && !p.vec_res))
-    return false;
-  const int nrt = (p.M + 255) / 256;
-  if (p.Cout % 128 || split) {
-    // a partial column block or column segments (fac_conv_nd_split): no
-    // residual tile, and enough row tiles that every persistent workgroup
-    // walks several (small late-block grids keep convnd_igemm's tiles)
-    if (!g_nd_pt_wide || res || nrt < g_nd_pt_wide) return false;
-  }
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  const int bn = res ? 128 : (p.Cout % 256 == 0 ? 256 : 128);
-  const int ny = (p.Cout + bn - 1) / bn;
-  int G = ncu / ny * ny;
-  if ((long long)nrt * ny < G) G = nrt * ny;
-  if (G <= 0) return false;
-  p.ny = 0;
-  if (res) convnd_pt<T, 128, true><<<G, 512, 0, st>>>(p, p);
-  else if (bn == 256) convnd_pt<T, 256><<<G, 512, 0, st>>>(p, p);
-  else convnd_pt<T, 128><<<G, 512, 0, st>>>(p, p);
-  return true;
+// convnd_igemm's tile, in the order the tiles are tried: 0 three 128 x 64
+// per CU, 1 64 x 64, 2 256 x 128, 3 two 128 x 64 per CU
+static int igemm_tile(const ConvP& p) {
+  // K <= 128 (1x1 expansions): memory-bound, so occupancy first — a 2-slot
+  // ring (48 KB) lets three 128 x 64 workgroups share a CU
+  if (p.ksteps <= 2 || (g_nd_occ3 && p.Cout <= 64 && p.ksteps <= g_nd_occ3)) return 0;
+  // small grids (S3D's late 4x7x7 / 2x3x3 stages): 64 x 64 tiles, three per CU
+  if ((long long)((p.M + 127) / 128) * ((p.Cout + 63) / 64) < 512) return 1;
+  // 256 x 128 tiles (8 waves, 144 KB ring, one per CU: 48 KB global -> LDS per
+  // 4.2 MFLOP, twice the 128 x 64 tile's intensity) when the grid still fills
+  // the chip at least once (ResNet's 7x7 layers: 392 tiles, 1.2-1.35x faster
+  // than 128 x 64 ones; same-box config 5 +2 %) and no column tile is half empty
+  return p.Cout % 128 == 0 && (long long)((p.M + 255) / 256) * ((p.Cout + 127) / 128) >= 256 ? 2 : 3;
+}
+template <int TILE>
+static bool igemm_matches(const ConvReq& r) { return igemm_tile(r.p) == TILE; }
+
+template <int BM, int BN, int WM, int WN, int OCC, int NS>
+static int igemm_launch(const ConvReq& r, hipStream_t st) {
+  ConvP p = r.p;
+  const dim3 g = conv_grid(p, (p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN);
+  return with_dtype(r.d->dtype, [&](auto t) {
+    using T = decltype(t);
+    // uniform-tap gather when every 64-deep K step lies in one tap (cin % 64),
+    // the per-lane tap gather otherwise; both with the interleaved glds issue
+    if (p.C8 % 8 == 0) convnd_igemm<T, BM, BN, WM, WN, OCC, NS, true, true><<<g, WM * WN * 64, 0, st>>>(p);
+    else convnd_igemm<T, BM, BN, WM, WN, OCC, NS, false, true><<<g, WM * WN * 64, 0, st>>>(p);
+  });
 }
 
-template <class T, bool UT, bool IL>
-static void launch_convnd_t(ConvP p, hipStream_t st) {
-  if constexpr (UT) {
-    if (launch_convnd_pt<T>(p, st)) return;
+// fac_conv_nd's routes.  The order is the precedence.
+static const Route<ConvReq> kConvRoutes[] = {
+    {"maxpool2s_pw", maxpool2s_pw_matches, maxpool2s_pw_launch, FAC_CONV_PREPOOL3S2},
+    {"conv_s2d4_mp", conv_s2d4_mp_matches, conv_s2d4_mp_launch, FAC_CONV_MAXPOOL3S2},
+    {"maxpool3_pw", maxpool3_pw_matches, maxpool3_pw_launch, FAC_CONV_MAXPOOL3S1},
+    {"conv_s2d4", conv_s2d4_matches, conv_s2d4_launch, 0},
+    {"pw_res", pw_res_split_matches, pw_res_split_launch, 0},
+    {"pw_res", pw_res_matches, pw_res_launch, 0},
+    {"pw_res2", pw_res2_matches, pw_res2_launch, 0},
+    {"conv_pw", conv_pw_matches, conv_pw_launch, 0},
+    {"conv_tk2", conv_tk2_matches, conv_tk2_launch, 0},
+    {"conv_tk", conv_tk_matches, conv_tk_launch, 0},
+    {"convnd_pt", convnd_pt_matches, convnd_pt_launch, 0},
+    {"convnd_igemm:128x64:3", igemm_matches<0>, igemm_launch<128, 64, 2, 2, 3, 2>, 0},
+    {"convnd_igemm:64x64:3", igemm_matches<1>, igemm_launch<64, 64, 2, 2, 3, 3>, 0},
+    {"convnd_igemm:256x128:1", igemm_matches<2>, igemm_launch<256, 128, 4, 2, 1, 3>, 0},
+    {"convnd_igemm:128x64:2", igemm_matches<3>, igemm_launch<128, 64, 2, 2, 2, 3>, 0},
+};
+
+// validates r's descriptor, fills r's derived fields and picks its route
+static const Route<ConvReq>* conv_route(ConvReq& r, int& status) {
+  const fac_conv_desc* d = r.d;
+  status = FAC_ERR_ARG;
+  if (!d || !d->in || !d->weight || !d->out || !dtype_ok(d->dtype)) return nullptr;
+  status = FAC_ERR_SHAPE;
+  if (!conv_dims_ok(d)) return nullptr;
+  // maxpool2s_pw's descriptors (another output size than the conv alone has)
+  // go to its own shape test
+  if (!(d->flags & FAC_CONV_PREPOOL3S2)) {
+    if (!conv_params(d, r.p)) return nullptr;
+    if (d->ldo < d->c_off + std::min(d->cout, r.split1) || d->c_off < 0) return nullptr;
+    status = FAC_ERR_ARG;
+    if ((d->flags & FAC_CONV_RESID) && (!d->residual || d->ldr < d->r_off + d->cout || d->r_off < 0)) return nullptr;
+    status = FAC_ERR_SHAPE;
+    if (conv_too_large(d)) return nullptr;
+    r.split = r.split1 < d->cout;
+    r.k_pad = r.p.Kp, r.cout_pad = cout_padded(d->cout), r.M = r.p.M;
+    r.p.out1 = r.out1, r.p.out2 = r.out2;
+    r.p.ldo1 = r.ldo1, r.p.ldo2 = r.ldo2, r.p.split1 = r.split1, r.p.split2 = r.split2;
+    if (r.split) r.p.vec_out = r.p.vec_out && r.ldo1 % 8 == 0 && r.ldo2 % 8 == 0;
   }
-  const int gx64 = (p.M + 63) / 64, gx128 = (p.M + 127) / 128, gx256 = (p.M + 255) / 256;
-  const int ny64 = (p.Cout + 63) / 64, ny128 = (p.Cout + 127) / 128;
-  constexpr int nd256_min = 256;  // 256 x 128 tiles only when they fill the chip at least once
-  if (p.ksteps <= 2 || (g_nd_occ3 && p.Cout <= 64 && p.ksteps <= g_nd_occ3)) {
-    // K <= 128 (1x1 expansions): memory-bound, so occupancy first — a 2-slot
-    // ring (48 KB) lets three 128 x 64 workgroups share a CU
-    const dim3 g = conv_grid(p, gx128, ny64);
-    convnd_igemm<T, 128, 64, 2, 2, 3, 2, UT, IL><<<g, 256, 0, st>>>(p);
-  } else if ((long long)gx128 * ny64 < 512) {
-    // small grids (S3D's late 4x7x7 / 2x3x3 stages): 64 x 64 tiles, three per CU
-    const dim3 g = conv_grid(p, gx64, ny64);
-    convnd_igemm<T, 64, 64, 2, 2, 3, 3, UT, IL><<<g, 256, 0, st>>>(p);
-  } else if (p.Cout % 128 == 0 && (long long)gx256 * ny128 >= nd256_min) {
-    // 256 x 128 tiles (8 waves, 144 KB ring, one per CU: 48 KB global -> LDS per
-    // 4.2 MFLOP, twice the 128 x 64 tile's intensity) when the grid still fills
-    // the chip at least once (ResNet's 7x7 layers: 392 tiles, 1.2-1.35x faster
-    // than 128 x 64 ones; same-box config 5 +2 %) and no column
-    // tile is half empty
-    const dim3 g = conv_grid(p, gx256, ny128);
-    convnd_igemm<T, 256, 128, 4, 2, 1, 3, UT, IL><<<g, 512, 0, st>>>(p);
-  } else {
-    const dim3 g = conv_grid(p, gx128, ny64);
-    convnd_igemm<T, 128, 64, 2, 2, 2, 3, UT, IL><<<g, 256, 0, st>>>(p);
-  }
+  return first_route(kConvRoutes, r, d->flags, status);
 }
 
-template <class T>
-static hipError_t launch_convnd(ConvP p, int cout_pad, hipStream_t st) {
-  (void)cout_pad;
-  // uniform-tap gather when every 64-deep K step lies in one tap (cin % 64),
-  // the per-lane tap gather otherwise; both with the interleaved glds issue
-  if (p.C8 % 8 == 0) launch_convnd_t<T, true, true>(p, st);
-  else launch_convnd_t<T, false, true>(p, st);
-  return hipGetLastError();
+static bool split_args_ok(const ConvReq& r) {
+  const fac_conv_desc* d = r.d;
+  return d && r.out1 && r.out2 && r.split1 > 0 && r.split1 % 8 == 0 && r.split2 > r.split1 && r.split2 % 8 == 0 &&
+         r.split2 < d->cout && r.ldo1 >= r.split2 - r.split1 && r.ldo2 >= d->cout - r.split2 &&
+         !(d->flags & (FAC_CONV_RESID | FAC_CONV_OUT_F32)) && d->ldo >= d->c_off + r.split1;
+}
+
+// an entry point (launch) and its route query (name); pick is conv_route / dual_route / pool_route
+template <class Req, class Pick>
+static int launch_route(Req r, Pick pick, void* stream) {
+  int status;
+  const Route<Req>* rt = pick(r, status);
+  return rt ? rt->launch(r, (hipStream_t)stream) : status;
+}
+template <class Req, class Pick>
+static const char* name_route(Req r, Pick pick, int* status) {
+  int st;
+  const Route<Req>* rt = pick(r, st);
+  if (status) *status = st;
+  return rt ? rt->name : nullptr;
+}
+
+// ---- fac_conv_nd_dual
+
+// 128-wide tiles: the 256-wide DUAL variant needs 256+ VGPRs and spills
+// (scratch traffic would also break the hand-counted vmcnt waits)
+static bool convnd_pt_dual_matches(const DualReq& r) { return convnd_pt_grid(r.p, 128) > 0; }
+static int convnd_pt_dual_launch(const DualReq& r, hipStream_t st) {
+  const int G = convnd_pt_grid(r.p, 128);
+  return with_dtype(r.d->dtype, [&](auto t) { convnd_pt<decltype(t), 128, false, true><<<G, 512, 0, st>>>(r.p, r.q); });
+}
+
+static const Route<DualReq> kDualRoutes[] = {
+    {"pw_res", pw_res_dual_matches, pw_res_dual_launch, 0},
+    {"pw_dual2", pw_dual2_matches, pw_dual2_launch, 0},
+    {"convnd_pt", convnd_pt_dual_matches, convnd_pt_dual_launch, 0},
+};
+
+static const Route<DualReq>* dual_route(DualReq& r, int& status) {
+  const fac_conv_desc *d = r.d, *ds = r.ds;
+  status = FAC_ERR_ARG;
+  if (!d || !ds || d->dtype != ds->dtype || !dtype_ok(d->dtype)) return nullptr;
+  if ((d->flags & ~(FAC_CONV_RELU | FAC_CONV_RELU2)) || ds->flags != 0) return nullptr;
+  status = FAC_ERR_SHAPE;
+  // both uniform-tap (cin % 64); the downsample conv has no output of its own
+  if (!d->in || !d->weight || !d->out || !ds->in || !ds->weight || d->cin % 64 || ds->cin % 64) return nullptr;
+  if (!conv_dims_ok(d) || !conv_dims_ok(ds) || !conv_params(d, r.p) || !conv_params(ds, r.q) || conv_too_large(d) ||
+      conv_too_large(ds))
+    return nullptr;
+  if (d->n != ds->n || d->od != ds->od || d->oh != ds->oh || d->ow != ds->ow || d->cout != ds->cout ||
+      d->cout % 128 || !r.p.vec_out || d->ldo < d->c_off + d->cout)
+    return nullptr;
+  return first_route(kDualRoutes, r, 0, status);
 }
 
 }  // namespace fac
@@ -4126,660 +4777,93 @@ extern "C" {
 
 int fac_conv_weight_layout(int cout, int cin, int kd, int kh, int kw, int* cout_pad, int* k_pad) {
   if (cout <= 0 || cin <= 0 || kd <= 0 || kh <= 0 || kw <= 0 || !cout_pad || !k_pad) return FAC_ERR_ARG;
-  *cout_pad = (cout + 127) / 128 * 128;
-  *k_pad = (kd * kh * kw * cin + 63) / 64 * 64;
+  *cout_pad = fac::cout_padded(cout);
+  *k_pad = fac::k_padded(cin, kd, kh, kw);
   return FAC_OK;
 }
 
-static int conv_nd_impl(const fac_conv_desc* d, void* out1, int ldo1, int split1, void* out2, int ldo2, int split2,
-                        void* stream) {
-  using namespace fac;
-  if (!d || !d->in || !d->weight || !d->out) return FAC_ERR_ARG;
-  if (d->dtype != FAC_DTYPE_BF16 && d->dtype != FAC_DTYPE_F16) return FAC_ERR_ARG;
-  if (d->cin <= 0 || d->cin % 8 || d->cout <= 0 || d->n <= 0 || d->d <= 0 || d->h <= 0 || d->w <= 0) return FAC_ERR_SHAPE;
-  // MaxPool3d((1,3,3), (1,2,2), (0,1,1)) over the input, then this 1x1x1
-  // 64 -> 64 conv (S3D's base.1 + base.2): maxpool2s_pw
-  if (d->flags & FAC_CONV_PREPOOL3S2) {
-    if ((d->flags & ~(FAC_CONV_RELU | FAC_CONV_PREPOOL3S2)) || out1 || out2 || d->kd != 1 || d->kh != 1 ||
-        d->kw != 1 || d->sd != 1 || d->sh != 1 || d->sw != 1 || d->pd || d->ph || d->pw || d->cin != 64 ||
-        d->cout != 64 || d->w != 56 || d->k_pad != 64 || d->od != d->d || d->oh != (d->h - 1) / 2 + 1 ||
-        d->ow != 28 || d->ldo % 8 || d->c_off % 8 || d->ldo < d->c_off + 64)
-      return FAC_ERR_ARG;
-    constexpr int RB = 4;
-    const int nunits = d->n * d->d * ((d->oh + RB - 1) / RB);
-    const int grid = (nunits + 7) / 8 * 8;
-    hipStream_t st = (hipStream_t)stream;
-    const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-    if (d->dtype == FAC_DTYPE_BF16)
-      fac::maxpool2s_pw<fac::BF16, 28, RB><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight,
-                                                                 d->bias, (uint16_t*)d->out, nunits, d->h, d->oh,
-                                                                 d->ldo, d->c_off, relu_on);
-    else
-      fac::maxpool2s_pw<fac::F16, 28, RB><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight,
-                                                                d->bias, (uint16_t*)d->out, nunits, d->h, d->oh,
-                                                                d->ldo, d->c_off, relu_on);
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || d->sd <= 0 || d->sh <= 0 || d->sw <= 0) return FAC_ERR_SHAPE;
-  if (d->pd < 0 || d->ph < 0 || d->pw < 0 || d->od <= 0 || d->oh <= 0 || d->ow <= 0) return FAC_ERR_SHAPE;
-  // output dims must be the floor-mode ones (every gathered tap then stays
-  // within the padded input)
-  if (d->od != (d->d + 2 * d->pd - d->kd) / d->sd + 1 || d->oh != (d->h + 2 * d->ph - d->kh) / d->sh + 1 ||
-      d->ow != (d->w + 2 * d->pw - d->kw) / d->sw + 1)
-    return FAC_ERR_SHAPE;
-  int cout_pad, k_pad;
-  fac_conv_weight_layout(d->cout, d->cin, d->kd, d->kh, d->kw, &cout_pad, &k_pad);
-  if (d->k_pad != k_pad) return FAC_ERR_SHAPE;
-  if (d->ldo < d->c_off + std::min(d->cout, split1) || d->c_off < 0) return FAC_ERR_SHAPE;
-  if ((d->flags & FAC_CONV_RESID) && (!d->residual || d->ldr < d->r_off + d->cout || d->r_off < 0)) return FAC_ERR_ARG;
-  const long long M = (long long)d->n * d->od * d->oh * d->ow;
-  if (M >= (1LL << 31) || (long long)d->n * d->d * d->h * d->w * d->cin >= (1LL << 40)) return FAC_ERR_SHAPE;
-  ConvP p;
-  p.in = (const uint16_t*)d->in;
-  p.w = (const uint16_t*)d->weight;
-  p.bias = d->bias;
-  p.res = (const uint16_t*)d->residual;
-  p.out = d->out;
-  p.D = d->d;
-  p.H = d->h;
-  p.W = d->w;
-  p.C8 = d->cin / 8;
-  p.Do = d->od;
-  p.Ho = d->oh;
-  p.Wo = d->ow;
-  p.Cout = d->cout;
-  p.KD = d->kd;
-  p.KH = d->kh;
-  p.KW = d->kw;
-  p.SD = d->sd;
-  p.SH = d->sh;
-  p.SW = d->sw;
-  p.PD = d->pd;
-  p.PH = d->ph;
-  p.PW = d->pw;
-  p.Kp = k_pad;
-  p.ksteps = k_pad / 64;
-  p.ktot8 = d->kd * d->kh * d->kw * (d->cin / 8);
-  p.ldo = d->ldo;
-  p.c_off = d->c_off;
-  p.ldr = d->ldr;
-  p.r_off = d->r_off;
-  p.flags = d->flags;
-  p.vec_out = (d->ldo % 8 == 0 && d->c_off % 8 == 0) ? 1 : 0;
-  p.vec_res = (d->ldr % 8 == 0 && d->r_off % 8 == 0) ? 1 : 0;
-  p.M = (int)M;
-  p.out1 = out1;
-  p.out2 = out2;
-  p.ldo1 = ldo1;
-  p.ldo2 = ldo2;
-  p.split1 = split1;
-  p.split2 = split2;
-  const bool split = split1 < d->cout;
-  if (split) p.vec_out = p.vec_out && ldo1 % 8 == 0 && ldo2 % 8 == 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool s2d4_shape = !split && d->kd == 1 && d->kh == 4 && d->kw == 4 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-                          d->pd == 0 && d->ph == 0 && d->pw == 0 && d->cin == 16 && d->cout == 64 && k_pad == 256 &&
-                          d->oh % 8 == 0 && d->ow % 28 == 0 && d->ldo == 64 && d->c_off == 0;
-  auto cu_count = [] {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-    return ncu;
-  };
-  // + MaxPool2d(3, 2, 1): only the space-to-depth first conv with ReLU
-  // (ResNet-50's conv1 -> bn1 -> relu -> maxpool), conv_s2d4_mp
-  if (d->flags & FAC_CONV_MAXPOOL3S2) {
-    if (!s2d4_shape || d->flags != (FAC_CONV_RELU | FAC_CONV_MAXPOOL3S2)) return FAC_ERR_ARG;
-    const int nimg = d->n * d->od, hp = d->oh / 2, wp = d->ow / 2, nstrip = nimg * (wp / 14);
-    const int grid = std::min(nstrip, 2 * cu_count());  // two resident (74 KB of LDS each)
-    if (d->dtype == FAC_DTYPE_BF16)
-      conv_s2d4_mp<BF16><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                               (uint16_t*)d->out, nstrip, d->h, d->w, hp, wp, k_pad);
-    else
-      conv_s2d4_mp<F16><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                              (uint16_t*)d->out, nstrip, d->h, d->w, hp, wp, k_pad);
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // MaxPool3d(3, 1, 1) over the input, then this 1x1x1 conv (S3D's
-  // Inception branch3): maxpool3_pw
-  if (d->flags & FAC_CONV_MAXPOOL3S1) {
-    const int S = d->h;
-    if (split || (d->flags & ~(FAC_CONV_RELU | FAC_CONV_MAXPOOL3S1)) || d->kd != 1 || d->kh != 1 || d->kw != 1 ||
-        d->sd != 1 || d->sh != 1 || d->sw != 1 || d->pd || d->ph || d->pw || d->w != S ||
-        !(S == 14 || S == 7 || S == 3) || d->cout % 32 || d->ldo % 8 || d->c_off % 8)
-      return FAC_ERR_ARG;
-    // frames per unit: 196 positions at 7 x 7 when the clip allows, 18 at 3 x 3
-    // frames per unit at 7 x 7: 2 by default (98 positions; fac_set_option
-    // "pool3_g" 1 / 2 / 4 forces one where the clip allows), at 3 x 3: 2
-    const int g7 = g_pool3_g ? g_pool3_g : 2;
-    const int G = S == 14 ? 1 : (S == 7 ? (d->d % g7 == 0 ? g7 : (d->d % 2 == 0 ? 2 : 1)) : (d->d % 2 == 0 ? 2 : 1));
-    const int nunits = d->n * (d->d / G);
-    // 128 columns per workgroup where cout allows (the pooled image is built
-    // once per unit instead of once per 64-column block), else 64 / 32
-    const int nct = d->cout % 128 == 0 ? 4 : (d->cout % 64 == 0 ? 2 : 1);
-    const dim3 grid((nunits + 7) / 8 * 8, d->cout / (32 * nct));
-    const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-    const uint16_t* in = (const uint16_t*)d->in;
-    const uint16_t* wt = (const uint16_t*)d->weight;
-    uint16_t* o = (uint16_t*)d->out;
-#define FAC_MPW(TT, SS, GG, NN)                                                                                     \
-  maxpool3_pw<TT, SS, GG, NN><<<grid, 256, 0, st>>>(in, wt, d->bias, o, nunits, d->d, d->cin, k_pad, d->ldo, d->c_off, \
-                                                     relu_on)
-#define FAC_MPW_S(TT, NN)                      \
-  do {                                         \
-    if (S == 14) FAC_MPW(TT, 14, 1, NN);       \
-    else if (S == 7 && G == 4) FAC_MPW(TT, 7, 4, NN); \
-    else if (S == 7 && G == 2) FAC_MPW(TT, 7, 2, NN); \
-    else if (S == 7) FAC_MPW(TT, 7, 1, NN);    \
-    else if (G == 2) FAC_MPW(TT, 3, 2, NN);    \
-    else FAC_MPW(TT, 3, 1, NN);                \
-  } while (0)
-    if (d->dtype == FAC_DTYPE_BF16) {
-      if (nct == 4) FAC_MPW_S(BF16, 4);
-      else if (nct == 2) FAC_MPW_S(BF16, 2);
-      else FAC_MPW_S(BF16, 1);
-    } else {
-      if (nct == 4) FAC_MPW_S(F16, 4);
-      else if (nct == 2) FAC_MPW_S(F16, 2);
-      else FAC_MPW_S(F16, 1);
-    }
-#undef FAC_MPW_S
-#undef FAC_MPW
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // the space-to-depth first conv (4x4/1 over 16-channel cells, cout 64, no
-  // residual, dense output): its own kernel (conv_s2d4)
-  if (s2d4_shape && (d->flags & ~FAC_CONV_RELU) == 0) {
-    const int nimg = d->n * d->od, nbox = nimg * (d->oh / 8) * (d->ow / 28);
-    const int grid = std::min(nbox, 2 * cu_count());  // two resident (two halo buffers + weights: 56 KB each)
-    const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-    if (d->dtype == FAC_DTYPE_BF16)
-      conv_s2d4<BF16><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                            (uint16_t*)d->out, nbox, d->h, d->w, d->oh, d->ow, k_pad, relu_on);
-    else
-      conv_s2d4<F16><<<grid, 256, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                           (uint16_t*)d->out, nbox, d->h, d->w, d->oh, d->ow, k_pad, relu_on);
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // S3D's merged Inception heads at K = 192 / 256 (fac_conv_nd_split, 1x1,
-  // relu(conv + b) into up to three column segments): pw_res PLAIN, 128-wide
-  // column blocks over the zero-padded weight rows
-  if (g_pw_res && split && d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-      d->pd == 0 && d->ph == 0 && d->pw == 0 && !(d->flags & ~FAC_CONV_RELU) && k_pad == d->cin &&
-      (d->cin == 192 || d->cin == 256) && d->ldo % 8 == 0 && d->c_off % 8 == 0 && ldo1 % 8 == 0 && ldo2 % 8 == 0 &&
-      split1 % 8 == 0 && (split2 == INT_MAX || split2 % 8 == 0) && cout_pad % 128 == 0) {
-    const int ny = cout_pad / 128, ncu = cu_count();
-    const int G = std::max(ny, ncu / ny * ny);
-    const int r1 = (d->flags & FAC_CONV_RELU) != 0;
-    const uint16_t* in = (const uint16_t*)d->in;
-    const uint16_t* wt = (const uint16_t*)d->weight;
-#define FAC_PWS(TT, KC)                                                                                              \
-  pw_res<TT, KC, 128, 64, 2><<<G, 512, 0, st>>>(in, wt, d->bias, nullptr, (uint16_t*)d->out, (int)M, k_pad, d->ldo, \
-                                                d->c_off, 0, 0, ny, r1, 0, nullptr, nullptr, nullptr, d->cout,      \
-                                                (uint16_t*)out1, ldo1, split1, (uint16_t*)out2, ldo2, split2)
-    if (d->dtype == FAC_DTYPE_BF16) {
-      if (d->cin == 192) FAC_PWS(BF16, 6);
-      else FAC_PWS(BF16, 8);
-    } else {
-      if (d->cin == 192) FAC_PWS(F16, 6);
-      else FAC_PWS(F16, 8);
-    }
-#undef FAC_PWS
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // the bottleneck conv3 + identity at K = 128 / 256 (ResNet-50 layer2 /
-  // layer3, relu(relu(conv + b) + residual)): pw_res
-  if (g_pw_res && !split && d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-      d->pd == 0 && d->ph == 0 && d->pw == 0 && (d->flags & FAC_CONV_RESID) &&
-      !(d->flags & ~(FAC_CONV_RELU | FAC_CONV_RESID | FAC_CONV_RELU2)) && k_pad == d->cin &&
-      ((d->cin == 128 && d->cout % 256 == 0) || (d->cin == 256 && d->cout % 128 == 0)) && d->ldo % 8 == 0 &&
-      d->c_off % 8 == 0 && d->ldr % 8 == 0 && d->r_off % 8 == 0) {
-    const int bn = d->cin == 128 ? 256 : 128, ny = d->cout / bn;
-    const int ncu = cu_count();
-    const int G = std::max(ny, ncu / ny * ny);
-    const int r1 = (d->flags & FAC_CONV_RELU) != 0, r2 = (d->flags & FAC_CONV_RELU2) != 0;
-    const uint16_t* in = (const uint16_t*)d->in;
-    const uint16_t* wt = (const uint16_t*)d->weight;
-    const uint16_t* res = (const uint16_t*)d->residual;
-    uint16_t* o = (uint16_t*)d->out;
-    const int mi = (int)M;
-#define FAC_PWR(TT, KC, BNN) \
-  pw_res<TT, KC, BNN, 64><<<G, 512, 0, st>>>(in, wt, d->bias, res, o, mi, k_pad, d->ldo, d->c_off, d->ldr, d->r_off, ny, r1, r2, \
-                                             nullptr, nullptr, nullptr, INT_MAX, nullptr, 0, INT_MAX, nullptr, 0, INT_MAX)
-    if (d->dtype == FAC_DTYPE_BF16) {
-      if (d->cin == 128) FAC_PWR(BF16, 4, 256);
-      else FAC_PWR(BF16, 8, 128);
-    } else {
-      if (d->cin == 128) FAC_PWR(F16, 4, 256);
-      else FAC_PWR(F16, 8, 128);
-    }
-#undef FAC_PWR
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // layer4's conv3 + identity (K 512, cout % 256 == 0): pw_res2, weights in
-  // VGPRs ("pw_res" 2 routes it back to convnd_pt for A/B)
-  if (g_pw_res == 1 && !split && d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 &&
-      d->sw == 1 && d->pd == 0 && d->ph == 0 && d->pw == 0 && (d->flags & FAC_CONV_RESID) &&
-      !(d->flags & ~(FAC_CONV_RELU | FAC_CONV_RESID | FAC_CONV_RELU2)) && k_pad == d->cin && d->cin == 512 &&
-      d->cout % 256 == 0 && d->ldo % 8 == 0 && d->c_off % 8 == 0 && d->ldr % 8 == 0 && d->r_off % 8 == 0) {
-    const int ny = d->cout / 256, ncu = cu_count(), G = std::max(ny, ncu / ny * ny);
-    const int r1 = (d->flags & FAC_CONV_RELU) != 0, r2 = (d->flags & FAC_CONV_RELU2) != 0;
-#define FAC_PWR2(TT)                                                                                            \
-  pw_res2<TT><<<G, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,                 \
-                                 (const uint16_t*)d->residual, (uint16_t*)d->out, (int)M, k_pad, d->ldo, d->c_off, \
-                                 d->ldr, d->r_off, ny, r1, r2)
-    if (d->dtype == FAC_DTYPE_BF16) FAC_PWR2(BF16);
-    else FAC_PWR2(F16);
-#undef FAC_PWR2
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // stride-1 1x1 convs with K = cin in {64, 128, 256}: conv_pw
-  // K 128 / 256 1x1s with cout % 128 == 0 go to convnd_pt instead: config 5
-  // +1.2 % same-box (layer3's 256 -> 1024 + residual 160 -> 145 us)
-  const bool to_pt = (d->cin == 128 || d->cin == 256) && d->cout % 128 == 0;
-  if (!split && !to_pt && d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-      d->pd == 0 && d->ph == 0 && d->pw == 0 && (d->cin == 64 || d->cin == 128 || d->cin == 256) &&
-      k_pad == d->cin &&
-      d->cout % 64 == 0 && d->ldo % 8 == 0 && d->c_off % 8 == 0 && !(d->flags & FAC_CONV_OUT_F32) &&
-      (!(d->flags & FAC_CONV_RESID) || (d->ldr % 8 == 0 && d->r_off % 8 == 0))) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-    const bool r = d->flags & FAC_CONV_RESID;
-    const int ny = d->cout / 64;
-    // rows per tile and the LDS-bound residency: weights 64 x cin, two A
-    // buffers of bm x cin (+ two residual blocks of bm x 64), 160 KB per CU
-    const int bm = d->cin == 64 ? 128 : 64;
-    const int lds = 128 * d->cin + 4 * bm * d->cin + (r ? 256 * bm : 0);
-    const int occ = std::min(3, 163840 / lds);
-    const int ntiles = (int)((M + bm - 1) / bm);
-    // one persistent workgroup per resident slot over all column blocks, a
-    // multiple of 8 row slots so a row tile's column blocks share an XCD
-    int gx = std::max(8, (occ * ncu / ny) / 8 * 8);
-    gx = std::min(gx, ntiles);
-    const dim3 grid(gx, ny);
-    const uint16_t* res = (const uint16_t*)d->residual;
-    uint16_t* o = (uint16_t*)d->out;
-    const uint16_t* in = (const uint16_t*)d->in;
-    const uint16_t* wt = (const uint16_t*)d->weight;
-    const int mi = (int)M;
-#define FAC_PW(TT, KC, RT, R) \
-  conv_pw<TT, KC, RT, R><<<grid, 256, 0, st>>>(in, wt, d->bias, res, o, mi, k_pad, d->ldo, d->c_off, d->ldr, d->r_off, d->flags)
-    if (d->dtype == FAC_DTYPE_BF16) {
-      if (d->cin == 64) r ? FAC_PW(BF16, 2, 2, true) : FAC_PW(BF16, 2, 2, false);
-      else if (d->cin == 128) r ? FAC_PW(BF16, 4, 1, true) : FAC_PW(BF16, 4, 1, false);
-      else r ? FAC_PW(BF16, 8, 1, true) : FAC_PW(BF16, 8, 1, false);
-    } else {
-      if (d->cin == 64) r ? FAC_PW(F16, 2, 2, true) : FAC_PW(F16, 2, 2, false);
-      else if (d->cin == 128) r ? FAC_PW(F16, 4, 1, true) : FAC_PW(F16, 4, 1, false);
-      else r ? FAC_PW(F16, 8, 1, true) : FAC_PW(F16, 8, 1, false);
-    }
-#undef FAC_PW
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // S3D's temporal (kd,1,1) convs with 8 output frames: conv_tk (LDS slab per
-  // 16 positions, the last one of a clip partial when 16 does not divide h*w)
-  if (!split && d->kh == 1 && d->kw == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && d->od == 8 &&
-      d->cin % 64 == 0 && d->cout % 64 == 0 && d->ldo % 4 == 0 &&
-      d->c_off % 4 == 0 &&
-      (d->flags & ~FAC_CONV_RELU) == 0 && k_pad == d->kd * d->cin) {
-    const int ks = d->kd * d->cin / 32, slab = d->d * 16 * d->cin;
-    const int db = ks * 2048 + 2 * slab <= 81920 ? 2 : (ks * 2048 + slab <= 81920 ? 1 : 0);
-    const bool k3 = d->kd == 3 && d->sd == 1 && d->pd == 1 && d->d == 8;
-    const bool k7 = d->kd == 7 && d->sd == 2 && d->pd == 3 && d->d == 16;
-    // slices of KC 32-channel chunks (every chunk of a unit in one or two
-    // steps: fewer per-step barriers and slice issues per MFMA), 3 ring slots
-    const int tk2_kc = d->cin == 192 ? 3 : (d->cin == 128 ? 4 : 2);
-    if ((k3 || k7) && (d->cin == 64 || d->cin == 128 || d->cin == 192) &&
-        ks * 2048 + 128 + 3 * tk2_kc * d->d * 512 <= 81920 &&
-        d->cin >= 64) {  // >= 2 slices per unit: at most R/2 store batches per wait window
-      int dev = 0, ncu = 256;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-        ncu = 256;
-      const int nunits = d->n * ((d->h * d->w + 15) / 16);
-      const int nbk = d->cout / 64;
-      const int nslot = (std::min(nunits, ncu) + 7) / 8 * 8;
-      const dim3 grid(nslot * nbk);
-      const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-#define FAC_TK2(TT, DP, KD, SD, KC)                                                                          \
-  conv_tk2<TT, DP, KD, SD, KC, 3><<<grid, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,  \
-                                                 (uint16_t*)d->out, nunits, d->h * d->w, d->cin, k_pad, d->ldo, \
-                                                 d->c_off, relu_on, nbk, nslot)
-#define FAC_TK2W(TT, DP, KD, SD, KC, WR)                                                                       \
-  conv_tk2<TT, DP, KD, SD, KC, 3, WR><<<grid, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight,  \
-                                                            d->bias, (uint16_t*)d->out, nunits, d->h * d->w,      \
-                                                            d->cin, k_pad, d->ldo, d->c_off, relu_on, nbk, nslot)
-      if (d->dtype == FAC_DTYPE_BF16) {
-        if (k7) FAC_TK2(BF16, 2, 7, 2, 2);
-        else if (tk2_kc == 3 && g_tk_wreg) FAC_TK2W(BF16, 1, 3, 1, 6, 6);
-        else if (tk2_kc == 3) FAC_TK2(BF16, 1, 3, 1, 3);
-        else if (tk2_kc == 4 && g_tk_wreg) FAC_TK2W(BF16, 1, 3, 1, 4, 4);
-        else if (tk2_kc == 4) FAC_TK2(BF16, 1, 3, 1, 4);
-        else FAC_TK2(BF16, 1, 3, 1, 2);
-      } else {
-        if (k7) FAC_TK2(F16, 2, 7, 2, 2);
-        else if (tk2_kc == 3 && g_tk_wreg) FAC_TK2W(F16, 1, 3, 1, 6, 6);
-        else if (tk2_kc == 3) FAC_TK2(F16, 1, 3, 1, 3);
-        else if (tk2_kc == 4 && g_tk_wreg) FAC_TK2W(F16, 1, 3, 1, 4, 4);
-        else if (tk2_kc == 4) FAC_TK2(F16, 1, 3, 1, 4);
-        else FAC_TK2(F16, 1, 3, 1, 2);
-      }
-#undef FAC_TK2
-#undef FAC_TK2W
-      return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-    }
-    if (db) {
-      int dev = 0, ncu = 256;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-        ncu = 256;
-      const int nunits = d->n * ((d->h * d->w + 15) / 16);
-      const int nbk = d->cout / 64;
-      // unit slots: a multiple of 8 (slot = 8 * hi + lo, see conv_tk), at most
-      // one per CU and per unit
-      const int nslot = (std::min(nunits, ncu) + 7) / 8 * 8;
-      const dim3 grid(nslot * nbk);
-      const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-      if (d->dtype == FAC_DTYPE_BF16)
-        conv_tk<BF16><<<grid, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                            (uint16_t*)d->out, nunits, d->h * d->w, d->d, d->cin, d->kd, d->sd,
-                                            d->pd, k_pad, d->ldo, d->c_off, relu_on, db, nbk, nslot);
-      else
-        conv_tk<F16><<<grid, 512, 0, st>>>((const uint16_t*)d->in, (const uint16_t*)d->weight, d->bias,
-                                           (uint16_t*)d->out, nunits, d->h * d->w, d->d, d->cin, d->kd, d->sd,
-                                           d->pd, k_pad, d->ldo, d->c_off, relu_on, db, nbk, nslot);
-      return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-    }
-  }
-  const hipError_t e = d->dtype == FAC_DTYPE_BF16 ? launch_convnd<BF16>(p, cout_pad, st) : launch_convnd<F16>(p, cout_pad, st);
-  return e == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-}
-
 int fac_conv_nd(const fac_conv_desc* d, void* stream) {
-  return conv_nd_impl(d, nullptr, 0, INT_MAX, nullptr, 0, INT_MAX, stream);
+  return fac::launch_route(fac::ConvReq{d, nullptr, nullptr, 0, 0, INT_MAX, INT_MAX}, fac::conv_route, stream);
 }
 
-static int conv_s2d4_clip_impl(const fac_conv_desc* d, const void* clip, bool u8, int h, int w, int pad_before,
-                               void* stream) {
-  using namespace fac;
-  if (!d || !clip || !d->weight || !d->out || (d->dtype != FAC_DTYPE_BF16 && d->dtype != FAC_DTYPE_F16))
-    return FAC_ERR_ARG;
-  if ((d->flags & ~FAC_CONV_RELU) != 0 || h <= 0 || w <= 0 || h % 2 || w % 2 || pad_before < 0 || d->n <= 0 ||
-      d->d <= 0)
-    return FAC_ERR_ARG;
-  int cout_pad, k_pad;
-  fac_conv_weight_layout(d->cout, d->cin, d->kd, d->kh, d->kw, &cout_pad, &k_pad);
-  // the conv fac_conv_nd would run on fac_pack_input_s2d(clip)'s cells: 4x4/1
-  // over 16-channel cells, cout 64, no padding, dense output, 8x28 boxes
-  const bool shape = d->kd == 1 && d->kh == 4 && d->kw == 4 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-                     d->pd == 0 && d->ph == 0 && d->pw == 0 && d->cin == 16 && d->cout == 64 && d->k_pad == k_pad &&
-                     k_pad == 256 && d->od == d->d && d->oh == d->h - 3 && d->ow == d->w - 3 && d->oh % 8 == 0 &&
-                     d->ow % 28 == 0 && d->ldo == 64 && d->c_off == 0 && d->h >= h / 2 + pad_before &&
-                     d->w >= w / 2 + pad_before;
-  if (!shape) return FAC_ERR_SHAPE;
-  if ((long long)d->n * d->d * 3 * h * w >= (1LL << 40)) return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      ncu <= 0)
-    ncu = 256;
-  const int nimg = d->n * d->od, nbox = nimg * (d->oh / 8) * (d->ow / 28);
-  const int grid = std::min(nbox, 2 * ncu);
-  const int relu_on = (d->flags & FAC_CONV_RELU) != 0;
-  hipStream_t st = (hipStream_t)stream;
-#define FAC_S2DC(TT, IN)                                                                                          \
-  conv_s2d4<TT, IN><<<grid, 256, 0, st>>>(clip, (const uint16_t*)d->weight, d->bias, (uint16_t*)d->out, nbox, d->h, \
-                                          d->w, d->oh, d->ow, k_pad, relu_on, d->d, h, w, pad_before)
-  if (d->dtype == FAC_DTYPE_BF16) u8 ? FAC_S2DC(BF16, 2) : FAC_S2DC(BF16, 1);
-  else u8 ? FAC_S2DC(F16, 2) : FAC_S2DC(F16, 1);
-#undef FAC_S2DC
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+int fac_conv_nd_split(const fac_conv_desc* d, void* out1, int ldo1, int split1, void* out2, int ldo2, int split2,
+                      void* stream) {
+  const fac::ConvReq r{d, out1, out2, ldo1, ldo2, split1, split2};
+  return fac::split_args_ok(r) ? fac::launch_route(r, fac::conv_route, stream) : FAC_ERR_ARG;
+}
+
+const char* fac_conv_nd_route(const fac_conv_desc* d, int split1, int split2, int* status) {
+  fac::ConvReq r{d, nullptr, nullptr, 0, 0, INT_MAX, INT_MAX};
+  if (d && (split1 != INT_MAX || split2 != INT_MAX)) {  // fac_conv_nd_split into dense segments
+    r = fac::ConvReq{d, d->out, d->out, split2 - split1, d->cout - split2, split1, split2};
+    if (d->out && !fac::split_args_ok(r)) r.d = nullptr;  // rejected as a null descriptor is: FAC_ERR_ARG
+  }
+  return fac::name_route(r, fac::conv_route, status);
+}
+
+int fac_conv_nd_dual(const fac_conv_desc* d, const fac_conv_desc* ds, void* stream) {
+  return fac::launch_route(fac::DualReq{d, ds}, fac::dual_route, stream);
+}
+
+const char* fac_conv_nd_dual_route(const fac_conv_desc* d, const fac_conv_desc* ds, int* status) {
+  return fac::name_route(fac::DualReq{d, ds}, fac::dual_route, status);
 }
 
 int fac_conv_s2d4_clip(const fac_conv_desc* d, const float* clip, int h, int w, int pad_before, void* stream) {
-  return conv_s2d4_clip_impl(d, clip, false, h, w, pad_before, stream);
+  return fac::conv_s2d4_clip<1>(d, clip, h, w, pad_before, stream);
 }
 
 int fac_conv_s2d4_clip_u8(const fac_conv_desc* d, const uint8_t* clip, int h, int w, int pad_before, void* stream) {
-  return conv_s2d4_clip_impl(d, clip, true, h, w, pad_before, stream);
+  return fac::conv_s2d4_clip<2>(d, clip, h, w, pad_before, stream);
 }
 
 int fac_s3d_base0_u8(const fac_conv_desc* sdsc, const fac_conv_desc* tdsc, const uint8_t* clip, int h, int w,
                      int pad_before, void* stream) {
   using namespace fac;
-  if (!sdsc || !tdsc || !clip || !sdsc->weight || !tdsc->weight || !tdsc->out || sdsc->dtype != tdsc->dtype ||
-      (sdsc->dtype != FAC_DTYPE_BF16 && sdsc->dtype != FAC_DTYPE_F16))
-    return FAC_ERR_ARG;
-  if (((sdsc->flags | tdsc->flags) & ~FAC_CONV_RELU) != 0 || pad_before < 0) return FAC_ERR_ARG;
-  int cps, kps, cpt, kpt;
-  fac_conv_weight_layout(sdsc->cout, sdsc->cin, sdsc->kd, sdsc->kh, sdsc->kw, &cps, &kps);
-  fac_conv_weight_layout(tdsc->cout, tdsc->cin, tdsc->kd, tdsc->kh, tdsc->kw, &cpt, &kpt);
-  // the spatial half as fac_conv_s2d4_clip_u8 takes it (4x4/1 over 16-channel
-  // cells of 16 frames, a 56 x 56 output), the temporal half as conv_tk2<2,7,2>
-  const bool sp = sdsc->kd == 1 && sdsc->kh == 4 && sdsc->kw == 4 && sdsc->sd == 1 && sdsc->sh == 1 && sdsc->sw == 1 &&
-                  sdsc->pd == 0 && sdsc->ph == 0 && sdsc->pw == 0 && sdsc->cin == 16 && sdsc->cout == 64 &&
-                  sdsc->k_pad == kps && kps == 256 && sdsc->d == 16 && sdsc->od == 16 && sdsc->oh == 56 &&
+  if (!conv_pair_ok(sdsc, tdsc, clip) || pad_before < 0) return FAC_ERR_ARG;
+  const int kpt = k_padded(tdsc);
+  // the spatial half as fac_conv_s2d4_clip_u8 takes it (16 frames, a 56 x 56
+  // output), the temporal half as conv_tk2<2,7,2>
+  const bool sp = is_s2d4(sdsc) && sdsc->k_pad == 256 && sdsc->d == 16 && sdsc->od == 16 && sdsc->oh == 56 &&
                   sdsc->ow == 56 && sdsc->h == 59 && sdsc->w == 59 && h % 2 == 0 && w % 2 == 0 &&
                   sdsc->h >= h / 2 + pad_before && sdsc->w >= w / 2 + pad_before;
   const bool tp = tdsc->kd == 7 && tdsc->kh == 1 && tdsc->kw == 1 && tdsc->sd == 2 && tdsc->sh == 1 && tdsc->sw == 1 &&
                   tdsc->pd == 3 && tdsc->ph == 0 && tdsc->pw == 0 && tdsc->cin == 64 && tdsc->cout == 64 &&
-                  tdsc->k_pad == kpt && kpt == 7 * 64 && tdsc->n == sdsc->n && tdsc->d == 16 && tdsc->h == 56 &&
-                  tdsc->w == 56 && tdsc->od == 8 && tdsc->oh == 56 && tdsc->ow == 56 && tdsc->ldo == 64 &&
-                  tdsc->c_off == 0;
+                  tdsc->k_pad == kpt && tdsc->n == sdsc->n && tdsc->d == 16 && tdsc->h == 56 && tdsc->w == 56 &&
+                  tdsc->od == 8 && tdsc->oh == 56 && tdsc->ow == 56 && tdsc->ldo == 64 && tdsc->c_off == 0;
   if (!sp || !tp || sdsc->n <= 0) return FAC_ERR_SHAPE;
   if ((long long)sdsc->n * 16 * 3 * h * w >= (1LL << 40)) return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      ncu <= 0)
-    ncu = 256;
   const int nunits = sdsc->n * (56 / 2) * (56 / 8);
-  const int grid = std::min(nunits, ncu);
-  const int rs = (sdsc->flags & FAC_CONV_RELU) != 0, rt = (tdsc->flags & FAC_CONV_RELU) != 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (sdsc->dtype == FAC_DTYPE_BF16)
-    s3d_base0<BF16><<<grid, 512, 0, st>>>(clip, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                          (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out,
-                                          nunits, h, w, pad_before, rs, rt);
-  else
-    s3d_base0<F16><<<grid, 512, 0, st>>>(clip, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                         (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out,
-                                         nunits, h, w, pad_before, rs, rt);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  const int grid = std::min(nunits, cu_count());
+  return with_dtype(sdsc->dtype, [&](auto t) {
+    s3d_base0<decltype(t)><<<grid, 512, 0, (hipStream_t)stream>>>(
+        clip, (const uint16_t*)sdsc->weight, sdsc->bias, 256, (const uint16_t*)tdsc->weight, tdsc->bias, kpt,
+        (uint16_t*)tdsc->out, nunits, h, w, pad_before, relu1(sdsc), relu1(tdsc));
+  });
 }
 
 int fac_sep_tiny(const fac_conv_desc* sdsc, const fac_conv_desc* tdsc, void* stream) {
   using namespace fac;
-  if (!sdsc || !tdsc || !sdsc->in || !sdsc->weight || !tdsc->weight || !tdsc->out || sdsc->dtype != tdsc->dtype ||
-      (sdsc->dtype != FAC_DTYPE_BF16 && sdsc->dtype != FAC_DTYPE_F16))
-    return FAC_ERR_ARG;
-  if (((sdsc->flags | tdsc->flags) & ~FAC_CONV_RELU) != 0) return FAC_ERR_ARG;
-  int cps, kps, cpt, kpt;
-  fac_conv_weight_layout(sdsc->cout, sdsc->cin, sdsc->kd, sdsc->kh, sdsc->kw, &cps, &kps);
-  fac_conv_weight_layout(tdsc->cout, tdsc->cin, tdsc->kd, tdsc->kh, tdsc->kw, &cpt, &kpt);
-  const bool sp = sdsc->cin == 16 && sdsc->cout == 32 && sdsc->kd == 1 && sdsc->kh == 3 && sdsc->kw == 3 &&
-                  sdsc->sd == 1 && sdsc->sh == 1 && sdsc->sw == 1 && sdsc->pd == 0 && sdsc->ph == 1 && sdsc->pw == 1 &&
-                  sdsc->d == 8 && sdsc->h == 14 && sdsc->w == 14 && sdsc->od == 8 && sdsc->oh == 14 && sdsc->ow == 14 &&
-                  sdsc->k_pad == kps && kps == 192 && sdsc->n > 0;
-  const bool tp = tdsc->cin == 32 && tdsc->cout == 32 && tdsc->kd == 3 && tdsc->kh == 1 && tdsc->kw == 1 &&
-                  tdsc->sd == 1 && tdsc->sh == 1 && tdsc->sw == 1 && tdsc->pd == 1 && tdsc->ph == 0 && tdsc->pw == 0 &&
-                  tdsc->n == sdsc->n && tdsc->d == 8 && tdsc->h == 14 && tdsc->w == 14 && tdsc->od == 8 &&
-                  tdsc->oh == 14 && tdsc->ow == 14 && tdsc->k_pad == kpt && kpt == 128 && tdsc->ldo % 8 == 0 &&
-                  tdsc->c_off % 8 == 0 && tdsc->ldo >= tdsc->c_off + 32;
-  if (!sp || !tp) return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      ncu <= 0)
-    ncu = 256;
-  const int grid = std::min(sdsc->n, ncu);
-  const int rs = (sdsc->flags & FAC_CONV_RELU) != 0, rt = (tdsc->flags & FAC_CONV_RELU) != 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (sdsc->dtype == FAC_DTYPE_BF16)
-    sep_tiny<BF16><<<grid, 512, 0, st>>>((const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                         (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out, sdsc->n,
-                                         tdsc->ldo, tdsc->c_off, rs, rt);
-  else
-    sep_tiny<F16><<<grid, 512, 0, st>>>((const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                        (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out, sdsc->n,
-                                        tdsc->ldo, tdsc->c_off, rs, rt);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  int kps, kpt;
+  if (const int rc = sep_check(sdsc, tdsc, 16, 32, 32, &kps, &kpt)) return rc;
+  const int grid = std::min(sdsc->n, cu_count());
+  return with_dtype(sdsc->dtype, [&](auto t) {
+    sep_tiny<decltype(t)><<<grid, 512, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps, (const uint16_t*)tdsc->weight,
+        tdsc->bias, kpt, (uint16_t*)tdsc->out, sdsc->n, tdsc->ldo, tdsc->c_off, relu1(sdsc), relu1(tdsc));
+  });
 }
 
 int fac_sep_mid(const fac_conv_desc* sdsc, const fac_conv_desc* tdsc, void* stream) {
   using namespace fac;
-  if (!sdsc || !tdsc || !sdsc->in || !sdsc->weight || !tdsc->weight || !tdsc->out || sdsc->dtype != tdsc->dtype ||
-      (sdsc->dtype != FAC_DTYPE_BF16 && sdsc->dtype != FAC_DTYPE_F16))
-    return FAC_ERR_ARG;
-  if (((sdsc->flags | tdsc->flags) & ~FAC_CONV_RELU) != 0) return FAC_ERR_ARG;
-  int cps, kps, cpt, kpt;
-  fac_conv_weight_layout(sdsc->cout, sdsc->cin, sdsc->kd, sdsc->kh, sdsc->kw, &cps, &kps);
-  fac_conv_weight_layout(tdsc->cout, tdsc->cin, tdsc->kd, tdsc->kh, tdsc->kw, &cpt, &kpt);
-  const bool sp = sdsc->cin == 32 && sdsc->cout == 128 && sdsc->kd == 1 && sdsc->kh == 3 && sdsc->kw == 3 &&
-                  sdsc->sd == 1 && sdsc->sh == 1 && sdsc->sw == 1 && sdsc->pd == 0 && sdsc->ph == 1 && sdsc->pw == 1 &&
-                  sdsc->d == 8 && sdsc->h == 14 && sdsc->w == 14 && sdsc->od == 8 && sdsc->oh == 14 && sdsc->ow == 14 &&
-                  sdsc->k_pad == kps && kps == 320 && sdsc->n > 0;
-  const bool tp = tdsc->cin == 128 && tdsc->cout == 96 && tdsc->kd == 3 && tdsc->kh == 1 && tdsc->kw == 1 &&
-                  tdsc->sd == 1 && tdsc->sh == 1 && tdsc->sw == 1 && tdsc->pd == 1 && tdsc->ph == 0 && tdsc->pw == 0 &&
-                  tdsc->n == sdsc->n && tdsc->d == 8 && tdsc->h == 14 && tdsc->w == 14 && tdsc->od == 8 &&
-                  tdsc->oh == 14 && tdsc->ow == 14 && tdsc->k_pad == kpt && kpt == 384 && tdsc->ldo % 8 == 0 &&
-                  tdsc->c_off % 8 == 0 && tdsc->ldo >= tdsc->c_off + 96;
-  if (!sp || !tp) return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      ncu <= 0)
-    ncu = 256;
-  const int nunits = sdsc->n * 7, grid = std::min(nunits, 2 * ncu);
-  const int rs = (sdsc->flags & FAC_CONV_RELU) != 0, rt = (tdsc->flags & FAC_CONV_RELU) != 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (sdsc->dtype == FAC_DTYPE_BF16)
-    sep_mid<BF16><<<grid, 384, 0, st>>>((const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                        (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out, nunits,
-                                        tdsc->ldo, tdsc->c_off, rs, rt);
-  else
-    sep_mid<F16><<<grid, 384, 0, st>>>((const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps,
-                                       (const uint16_t*)tdsc->weight, tdsc->bias, kpt, (uint16_t*)tdsc->out, nunits,
-                                       tdsc->ldo, tdsc->c_off, rs, rt);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-}
-
-int fac_conv_nd_split(const fac_conv_desc* d, void* out1, int ldo1, int split1, void* out2, int ldo2, int split2,
-                      void* stream) {
-  if (!d || !out1 || !out2 || split1 <= 0 || split1 % 8 || split2 <= split1 || split2 % 8 || split2 >= d->cout ||
-      ldo1 < split2 - split1 || ldo2 < d->cout - split2 || (d->flags & (FAC_CONV_RESID | FAC_CONV_OUT_F32)) ||
-      d->ldo < d->c_off + split1)
-    return FAC_ERR_ARG;
-  return conv_nd_impl(d, out1, ldo1, split1, out2, ldo2, split2, stream);
-}
-
-// the ConvP of a uniform-tap conv for convnd_pt (fac_conv_nd_dual); false if
-// the descriptor is malformed or not uniform-tap (cin % 64)
-static bool dual_convp(const fac_conv_desc* d, fac::ConvP& p, bool need_out) {
-  if (!d || !d->in || !d->weight || (need_out && !d->out)) return false;
-  if (d->cin <= 0 || d->cin % 64 || d->cout <= 0 || d->n <= 0 || d->d <= 0 || d->h <= 0 || d->w <= 0) return false;
-  if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || d->sd <= 0 || d->sh <= 0 || d->sw <= 0) return false;
-  if (d->pd < 0 || d->ph < 0 || d->pw < 0) return false;
-  if (d->od != (d->d + 2 * d->pd - d->kd) / d->sd + 1 || d->oh != (d->h + 2 * d->ph - d->kh) / d->sh + 1 ||
-      d->ow != (d->w + 2 * d->pw - d->kw) / d->sw + 1)
-    return false;
-  int cout_pad, k_pad;
-  fac_conv_weight_layout(d->cout, d->cin, d->kd, d->kh, d->kw, &cout_pad, &k_pad);
-  if (d->k_pad != k_pad) return false;
-  const long long M = (long long)d->n * d->od * d->oh * d->ow;
-  if (M >= (1LL << 31) || (long long)d->n * d->d * d->h * d->w * d->cin >= (1LL << 40)) return false;
-  p = fac::ConvP{};
-  p.in = (const uint16_t*)d->in;
-  p.w = (const uint16_t*)d->weight;
-  p.bias = d->bias;
-  p.out = d->out;
-  p.D = d->d;
-  p.H = d->h;
-  p.W = d->w;
-  p.C8 = d->cin / 8;
-  p.Do = d->od;
-  p.Ho = d->oh;
-  p.Wo = d->ow;
-  p.Cout = d->cout;
-  p.KD = d->kd;
-  p.KH = d->kh;
-  p.KW = d->kw;
-  p.SD = d->sd;
-  p.SH = d->sh;
-  p.SW = d->sw;
-  p.PD = d->pd;
-  p.PH = d->ph;
-  p.PW = d->pw;
-  p.Kp = k_pad;
-  p.ksteps = k_pad / 64;
-  p.ktot8 = d->kd * d->kh * d->kw * (d->cin / 8);
-  p.ldo = d->ldo;
-  p.c_off = d->c_off;
-  p.flags = d->flags;
-  p.vec_out = (d->ldo % 8 == 0 && d->c_off % 8 == 0) ? 1 : 0;
-  p.M = (int)M;
-  p.split1 = p.split2 = INT_MAX;
-  return true;
-}
-
-int fac_conv_nd_dual(const fac_conv_desc* d, const fac_conv_desc* ds, void* stream) {
-  using namespace fac;
-  if (!d || !ds || d->dtype != ds->dtype || (d->dtype != FAC_DTYPE_BF16 && d->dtype != FAC_DTYPE_F16)) return FAC_ERR_ARG;
-  if ((d->flags & ~(FAC_CONV_RELU | FAC_CONV_RELU2)) || ds->flags != 0) return FAC_ERR_ARG;
-  ConvP p, q;
-  if (!dual_convp(d, p, true) || !dual_convp(ds, q, false)) return FAC_ERR_SHAPE;
-  if (d->n != ds->n || d->od != ds->od || d->oh != ds->oh || d->ow != ds->ow || d->cout != ds->cout ||
-      d->cout % 128 || !p.vec_out || d->ldo < d->c_off + d->cout)
-    return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
-  // layer1's first block (64 -> 256 twice, the downsample at stride 1 over
-  // the same positions): pw_res DUAL
-  if (g_pw_res && d->cin == 64 && ds->cin == 64 && d->cout % 256 == 0 && p.KD * p.KH * p.KW == 1 &&
-      q.KD * q.KH * q.KW == 1 && p.SD * p.SH * p.SW == 1 && q.SD * q.SH * q.SW == 1 && !p.PD && !p.PH && !p.PW &&
-      !q.PD && !q.PH && !q.PW && p.Kp == 64 && q.Kp == 64) {
-    const int ny2 = d->cout / 256, G2 = std::max(ny2, ncu / ny2 * ny2);
-    const int r1 = (d->flags & FAC_CONV_RELU) != 0, r2 = (d->flags & FAC_CONV_RELU2) != 0;
-    hipStream_t st2 = (hipStream_t)stream;
-#define FAC_PWD(TT)                                                                                                     \
-  pw_res<TT, 2, 256, 128, 1><<<G2, 512, 0, st2>>>(p.in, p.w, p.bias, nullptr, (uint16_t*)p.out, p.M, 64, p.ldo,           \
-                                                   p.c_off, 0, 0, ny2, r1, r2, q.in, q.w, q.bias, INT_MAX, nullptr, 0, INT_MAX, \
-                                                   nullptr, 0, INT_MAX)
-    if (d->dtype == FAC_DTYPE_BF16) FAC_PWD(BF16);
-    else FAC_PWD(F16);
-#undef FAC_PWD
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // layer2's first block (conv3 128 -> 512 at 28^2, the downsample 256 -> 512
-  // at stride 2 over the 56^2 block input): pw_dual2
-  if (g_pw_res == 1 && ((d->cin == 128 && ds->cin == 256) || (d->cin == 256 && ds->cin == 512)) && d->cout % PWD2_BN == 0 && p.KD * p.KH * p.KW == 1 && q.KD * q.KH * q.KW == 1 &&
-      p.SD * p.SH * p.SW == 1 && q.SD == 1 && q.SH == q.SW && q.SH >= 1 && !p.PD && !p.PH && !p.PW && !q.PD &&
-      !q.PH && !q.PW && p.Kp == d->cin && q.Kp == ds->cin && p.D == 1 && q.D == 1 &&
-      (long long)q.H * q.W * d->n < (1LL << 31)) {  // (x positions as int)
-    const int ny2 = d->cout / PWD2_BN, G2 = std::max(ny2, ncu / ny2 * ny2);
-    const int r1 = (d->flags & FAC_CONV_RELU) != 0, r2 = (d->flags & FAC_CONV_RELU2) != 0;
-    hipStream_t st2 = (hipStream_t)stream;
-#define FAC_PWD2(TT, K3, KD, CW)                                                                              \
-  pw_dual2<TT, K3, KD, CW><<<G2, 512, 0, st2>>>(p.in, p.w, p.bias, q.in, q.w, q.bias, (uint16_t*)p.out, p.M, K3, KD, \
-                                                 p.ldo, p.c_off, ny2, p.Ho, p.Wo, q.H, q.W, q.SH, r1, r2)
-    if (d->cin == 128) {
-      if (d->dtype == FAC_DTYPE_BF16) FAC_PWD2(BF16, 128, 256, 64);
-      else FAC_PWD2(F16, 128, 256, 64);
-    } else {
-      if (d->dtype == FAC_DTYPE_BF16) FAC_PWD2(BF16, 256, 512, 32);
-      else FAC_PWD2(F16, 256, 512, 32);
-    }
-#undef FAC_PWD2
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  // 128-wide tiles: the 256-wide DUAL variant needs 256+ VGPRs and spills
-  // (scratch traffic would also break the hand-counted vmcnt waits)
-  const int nrt = (p.M + 255) / 256, ny = p.Cout / 128;
-  int G = ncu / ny * ny;
-  if ((long long)nrt * ny < G) G = nrt * ny;
-  if (G <= 0) return FAC_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == FAC_DTYPE_BF16) convnd_pt<BF16, 128, false, true><<<G, 512, 0, st>>>(p, q);
-  else convnd_pt<F16, 128, false, true><<<G, 512, 0, st>>>(p, q);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  int kps, kpt;
+  if (const int rc = sep_check(sdsc, tdsc, 32, 128, 96, &kps, &kpt)) return rc;
+  const int nunits = sdsc->n * 7, grid = std::min(nunits, 2 * cu_count());
+  return with_dtype(sdsc->dtype, [&](auto t) {
+    sep_mid<decltype(t)><<<grid, 384, 0, (hipStream_t)stream>>>(
+        (const uint16_t*)sdsc->in, (const uint16_t*)sdsc->weight, sdsc->bias, kps, (const uint16_t*)tdsc->weight,
+        tdsc->bias, kpt, (uint16_t*)tdsc->out, nunits, tdsc->ldo, tdsc->c_off, relu1(sdsc), relu1(tdsc));
+  });
 }
 
 int fac_bottleneck_pw2(const fac_conv_desc* c3, const fac_conv_desc* c1, void* stream) {
@@ -4787,11 +4871,10 @@ int fac_bottleneck_pw2(const fac_conv_desc* c3, const fac_conv_desc* c1, void* s
   if (!c3 || !c1 || !c3->in || !c3->weight || !c3->bias || !c3->out || !c3->residual || !c1->weight || !c1->bias ||
       !c1->out)
     return FAC_ERR_ARG;
-  if (c3->dtype != c1->dtype || (c3->dtype != FAC_DTYPE_BF16 && c3->dtype != FAC_DTYPE_F16)) return FAC_ERR_ARG;
+  if (c3->dtype != c1->dtype || !dtype_ok(c3->dtype)) return FAC_ERR_ARG;
   if (c3->flags != (FAC_CONV_RELU | FAC_CONV_RESID | FAC_CONV_RELU2) || c1->flags != FAC_CONV_RELU) return FAC_ERR_ARG;
   auto pw = [](const fac_conv_desc* d) {
-    return d->kd == 1 && d->kh == 1 && d->kw == 1 && d->sd == 1 && d->sh == 1 && d->sw == 1 && d->pd == 0 &&
-           d->ph == 0 && d->pw == 0 && d->od == d->d && d->oh == d->h && d->ow == d->w && d->c_off == 0;
+    return is_pointwise(d) && d->od == d->d && d->oh == d->h && d->ow == d->w && d->c_off == 0;
   };
   const bool l1 = c3->cin == 64 && c3->cout == 256 && c3->k_pad == 64 && c1->cin == 256 && c1->k_pad == 256 &&
                   (c1->cout == 64 || c1->cout == 128);
@@ -4802,110 +4885,24 @@ int fac_bottleneck_pw2(const fac_conv_desc* c3, const fac_conv_desc* c1, void* s
   if (c3->ldr % 8 || c3->r_off % 8 || c3->ldr < c3->r_off + c3->cout) return FAC_ERR_SHAPE;
   const long long M = (long long)c3->n * c3->d * c3->h * c3->w;
   if (M <= 0 || M >= (1LL << 31)) return FAC_ERR_SHAPE;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
-  hipStream_t st = (hipStream_t)stream;
-  if (l2) {
-    const int grid = (int)std::min<long long>((M + 15) / 16, ncu);
-    if (c3->dtype == FAC_DTYPE_BF16)
-      bneck_pw2_l2<BF16><<<grid, 512, 0, st>>>((const uint16_t*)c3->in, (const uint16_t*)c3->weight, c3->bias,
-                                               (const uint16_t*)c3->residual, (const uint16_t*)c1->weight, c1->bias,
-                                               (uint16_t*)c3->out, (uint16_t*)c1->out, (int)M, c3->k_pad, c1->k_pad,
-                                               c3->ldr, c3->r_off);
-    else
-      bneck_pw2_l2<F16><<<grid, 512, 0, st>>>((const uint16_t*)c3->in, (const uint16_t*)c3->weight, c3->bias,
-                                              (const uint16_t*)c3->residual, (const uint16_t*)c1->weight, c1->bias,
-                                              (uint16_t*)c3->out, (uint16_t*)c1->out, (int)M, c3->k_pad, c1->k_pad,
-                                              c3->ldr, c3->r_off);
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  const int ntiles = (int)((M + 63) / 64), grid = std::min(ntiles, ncu);
-#define FAC_PW2(TT, N)                                                                                           \
-  bneck_pw2<TT, N><<<grid, 512, 0, st>>>((const uint16_t*)c3->in, (const uint16_t*)c3->weight, c3->bias,         \
-                                         (const uint16_t*)c3->residual, (const uint16_t*)c1->weight, c1->bias,   \
-                                         (uint16_t*)c3->out, (uint16_t*)c1->out, (int)M, c3->k_pad, c1->k_pad,   \
-                                         c3->ldr, c3->r_off)
-  if (c3->dtype == FAC_DTYPE_BF16) {
-    if (c1->cout == 64) FAC_PW2(BF16, 64);
-    else FAC_PW2(BF16, 128);
-  } else {
-    if (c1->cout == 64) FAC_PW2(F16, 64);
-    else FAC_PW2(F16, 128);
-  }
-#undef FAC_PW2
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  // 16-row tiles at layer2, 64-row ones at layer1
+  const int grid = (int)std::min<long long>((M + (l2 ? 15 : 63)) / (l2 ? 16 : 64), cu_count());
+  return with_dtype(c3->dtype, [&](auto t) {
+    using T = decltype(t);
+    auto k = l2 ? bneck_pw2_l2<T> : c1->cout == 64 ? bneck_pw2<T, 64> : bneck_pw2<T, 128>;
+    k<<<grid, 512, 0, (hipStream_t)stream>>>((const uint16_t*)c3->in, (const uint16_t*)c3->weight, c3->bias,
+                                             (const uint16_t*)c3->residual, (const uint16_t*)c1->weight, c1->bias,
+                                             (uint16_t*)c3->out, (uint16_t*)c1->out, (int)M, c3->k_pad, c1->k_pad,
+                                             c3->ldr, c3->r_off);
+  });
 }
 
 int fac_pool_nd(const fac_pool_desc* d, void* stream) {
-  using namespace fac;
-  if (!d || !d->in || !d->out) return FAC_ERR_ARG;
-  if (d->dtype != FAC_DTYPE_BF16 && d->dtype != FAC_DTYPE_F16) return FAC_ERR_ARG;
-  if (d->c <= 0 || d->c % 8 || d->n <= 0 || d->od <= 0 || d->oh <= 0 || d->ow <= 0 || d->mode < 0 || d->mode > 1)
-    return FAC_ERR_SHAPE;
-  if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || d->sd <= 0 || d->sh <= 0 || d->sw <= 0) return FAC_ERR_SHAPE;
-  if (d->ldo % 8 || d->c_off % 8 || d->ldo < d->c_off + d->c) return FAC_ERR_SHAPE;
-  const long long total = (long long)d->n * d->od * d->oh * d->ow * (d->c / 8);
-  if (total >= (1LL << 31)) return FAC_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (d->mode == 0 && d->kd == 3 && d->kh == 3 && d->kw == 3 && d->sd == 1 && d->sh == 1 && d->sw == 1 &&
-      d->pd == 1 && d->ph == 1 && d->pw == 1 && d->od == d->d && d->oh == d->h && d->ow == d->w) {
-    if (g_pool_lds14 && d->h == 14 && d->w == 14 && d->c % 64 == 0 && d->ldo % 8 == 0) {
-      const long long nwg = (long long)d->n * (d->c / 64);
-      if (nwg >= (1LL << 31)) return FAC_ERR_SHAPE;
-      if (d->dtype == FAC_DTYPE_BF16)
-        maxpool3_lds14<BF16><<<(int)nwg, 256, 0, st>>>(*d);
-      else
-        maxpool3_lds14<F16><<<(int)nwg, 256, 0, st>>>(*d);
-      return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-    }
-    if (g_pool_roll && d->w == 7) {
-      const int zg = g_pool_roll == 1 ? d->d : std::min(g_pool_roll, d->d);
-      const long long rows = (long long)d->n * ((d->d + zg - 1) / zg) * d->h * (d->c / 8);
-      if (rows >= (1LL << 31)) return FAC_ERR_SHAPE;
-      const int nb = (int)((rows + 255) / 256);
-      if (d->dtype == FAC_DTYPE_BF16)
-        maxpool3_roll<BF16, 7><<<nb, 256, 0, st>>>(*d, (int)rows, zg);
-      else
-        maxpool3_roll<F16, 7><<<nb, 256, 0, st>>>(*d, (int)rows, zg);
-      return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-    }
-    const int zg = g_pool3_zg > 0 ? std::min(g_pool3_zg, d->d) : d->d;  // output frames per thread (default all)
-    const long long cols = (long long)d->n * ((d->d + zg - 1) / zg) * d->h * d->w * (d->c / 8);
-    if (cols >= (1LL << 31)) return FAC_ERR_SHAPE;
-    const int nb = (int)((cols + 255) / 256);
-    if (d->dtype == FAC_DTYPE_BF16)
-      maxpool3_s1<BF16><<<nb, 256, 0, st>>>(*d, (int)cols, zg);
-    else
-      maxpool3_s1<F16><<<nb, 256, 0, st>>>(*d, (int)cols, zg);
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
-  }
-  const int nb = (int)((total + 255) / 256);
-  // compile-time windows (branch-free taps) for the max pools of S3D / ResNet:
-  // floor-mode output dims and padding below the window keep a valid tap in
-  // every window (pool_nd takes anything else)
-  const bool floor_dims = d->od == (d->d + 2 * d->pd - d->kd) / d->sd + 1 &&
-                          d->oh == (d->h + 2 * d->ph - d->kh) / d->sh + 1 &&
-                          d->ow == (d->w + 2 * d->pw - d->kw) / d->sw + 1 && d->pd >= 0 && d->ph >= 0 &&
-                          d->pw >= 0 && d->pd < d->kd && d->ph < d->kh && d->pw < d->kw;
-  if (d->mode == 0 && g_pool_win && floor_dims) {
-    const bool bf = d->dtype == FAC_DTYPE_BF16;
-#define FAC_WIN(KD, KH, KW)                                                                                      \
-  if (d->kd == KD && d->kh == KH && d->kw == KW) {                                                            \
-    if (bf) pool_max_win<BF16, KD, KH, KW><<<nb, 256, 0, st>>>(*d, (int)total);                               \
-    else pool_max_win<F16, KD, KH, KW><<<nb, 256, 0, st>>>(*d, (int)total);                                   \
-    return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;                                            \
-  }
-    FAC_WIN(1, 3, 3)
-    FAC_WIN(3, 3, 3)
-    FAC_WIN(2, 2, 2)
-#undef FAC_WIN
-  }
-  if (d->dtype == FAC_DTYPE_BF16)
-    pool_nd<BF16><<<nb, 256, 0, st>>>(*d, (int)total);
-  else
-    pool_nd<F16><<<nb, 256, 0, st>>>(*d, (int)total);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  return fac::launch_route(fac::PoolReq{d, 0}, fac::pool_route, stream);
+}
+
+const char* fac_pool_nd_route(const fac_pool_desc* d, int* status) {
+  return fac::name_route(fac::PoolReq{d, 0}, fac::pool_route, status);
 }
 
 int fac_pack_input(int dtype, const void* src, int src_kind, int n, int s, float div, const float* mean3,
@@ -4913,49 +4910,34 @@ int fac_pack_input(int dtype, const void* src, int src_kind, int n, int s, float
   using namespace fac;
   if (!src || !out || n <= 0 || s <= 0 || c_pad < 8 || c_pad % 8 || (src_kind != 0 && src_kind != 1) || !(div > 0.f))
     return FAC_ERR_ARG;
-  if (dtype != FAC_DTYPE_BF16 && dtype != FAC_DTYPE_F16) return FAC_ERR_ARG;
   const float m[3] = {mean3 ? mean3[0] : 0.f, mean3 ? mean3[1] : 0.f, mean3 ? mean3[2] : 0.f};
   const float sd[3] = {std3 ? std3[0] : 1.f, std3 ? std3[1] : 1.f, std3 ? std3[2] : 1.f};
   const long long total = (long long)n * s;
   const int nb = (int)((total + 255) / 256);
-  hipStream_t st = (hipStream_t)stream;
-  uint16_t* o = (uint16_t*)out;
-#define FAC_PACK(TT, U)                                                                                      \
-  pack_input<TT, U><<<nb, 256, 0, st>>>(src, n, s, div, m[0], m[1], m[2], sd[0], sd[1], sd[2], o, c_pad)
-  if (dtype == FAC_DTYPE_BF16) {
-    if (src_kind == 0) FAC_PACK(BF16, true); else FAC_PACK(BF16, false);
-  } else {
-    if (src_kind == 0) FAC_PACK(F16, true); else FAC_PACK(F16, false);
-  }
-#undef FAC_PACK
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  return with_dtype(dtype, [&](auto t) {
+    auto k = src_kind == 0 ? pack_input<decltype(t), true> : pack_input<decltype(t), false>;
+    k<<<nb, 256, 0, (hipStream_t)stream>>>(src, n, s, div, m[0], m[1], m[2], sd[0], sd[1], sd[2],
+                                           (uint16_t*)out, c_pad);
+  });
 }
 
 int fac_pack_input_s2d(int dtype, const void* src, int src_kind, int n, int frames, int h, int w, int pad_before,
                        int pad_after, float div, const float* mean3, const float* std3, void* out, void* stream) {
   using namespace fac;
   if (!src || !out || n <= 0 || frames <= 0 || h <= 0 || w <= 0 || h % 2 || w % 2 || pad_before < 0 || pad_after < 0 ||
-      (src_kind != 0 && src_kind != 1) || !(div > 0.f))
+      (src_kind != 0 && src_kind != 1) || !(div > 0.f) || !dtype_ok(dtype))
     return FAC_ERR_ARG;
-  if (dtype != FAC_DTYPE_BF16 && dtype != FAC_DTYPE_F16) return FAC_ERR_ARG;
   const float m[3] = {mean3 ? mean3[0] : 0.f, mean3 ? mean3[1] : 0.f, mean3 ? mean3[2] : 0.f};
   const float sd[3] = {std3 ? std3[0] : 1.f, std3 ? std3[1] : 1.f, std3 ? std3[2] : 1.f};
   const long long total =
       (long long)n * frames * (h / 2 + pad_before + pad_after) * (w / 2 + pad_before + pad_after);
   if (total >= (1LL << 31) - 256) return FAC_ERR_SHAPE;  // the kernel indexes cells in 32 bits
   const int nb = (int)((total + 255) / 256);
-  hipStream_t st = (hipStream_t)stream;
-  uint16_t* o = (uint16_t*)out;
-#define FAC_PACK(TT, U)                                                                                         \
-  pack_input_s2d<TT, U><<<nb, 256, 0, st>>>(src, n * frames, frames, h, w, pad_before, pad_after, div, m[0], \
-                                            m[1], m[2], sd[0], sd[1], sd[2], o)
-  if (dtype == FAC_DTYPE_BF16) {
-    if (src_kind == 0) FAC_PACK(BF16, true); else FAC_PACK(BF16, false);
-  } else {
-    if (src_kind == 0) FAC_PACK(F16, true); else FAC_PACK(F16, false);
-  }
-#undef FAC_PACK
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  return with_dtype(dtype, [&](auto t) {
+    auto k = src_kind == 0 ? pack_input_s2d<decltype(t), true> : pack_input_s2d<decltype(t), false>;
+    k<<<nb, 256, 0, (hipStream_t)stream>>>(src, n * frames, frames, h, w, pad_before, pad_after, div, m[0], m[1],
+                                           m[2], sd[0], sd[1], sd[2], (uint16_t*)out);
+  });
 }
 
 size_t fac_kan_scratch_bytes(int rows, int in_f, int out_f) {
@@ -4975,13 +4957,13 @@ int fac_kan_linear(const float* x, int rows, int in_f, int out_f, const float* g
                                                                               (float*)partial);
   const int n = rows * out_f;
   kan_reduce<<<(n + 255) / 256, 256, 0, st>>>((const float*)partial, chunks, n, y);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  return fac::launch_status();
 }
 
 int fac_sigmoid(const float* x, float* y, int n, void* stream) {
   if (!x || !y || n <= 0) return FAC_ERR_ARG;
   fac::sigmoid_k<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(x, y, n);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  return fac::launch_status();
 }
 
 int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
@@ -4992,14 +4974,11 @@ int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, c
   if (h > 16 || w > 16 || cg % 16 || cg > 256 || h * w * cg > 16384 || (2 * h + 2 * w) * cg > 8192 ||
       (2 * h + 2 * w) > 64)
     return FAC_ERR_SHAPE;
-  const hipStream_t st = (hipStream_t)stream;
-  if (dtype == 0)
-    fac::ggca_k<fac::BF16><<<n * groups, 256, 0, st>>>((const uint16_t*)x, h, w, c, groups, w1, b1, bn4, w2, b2,
-                                                      (uint16_t*)out);
-  else
-    fac::ggca_k<fac::F16><<<n * groups, 256, 0, st>>>((const uint16_t*)x, h, w, c, groups, w1, b1, bn4, w2, b2,
-                                                     (uint16_t*)out);
-  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+  // (any dtype but bf16 runs as fp16)
+  return fac::with_dtype(dtype == FAC_DTYPE_BF16 ? FAC_DTYPE_BF16 : FAC_DTYPE_F16, [&](auto t) {
+    fac::ggca_k<decltype(t)><<<n * groups, 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, h, w, c, groups, w1, b1,
+                                                                          bn4, w2, b2, (uint16_t*)out);
+  });
 }
 
 }  // extern "C"

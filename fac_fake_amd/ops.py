@@ -210,11 +210,11 @@ class ConvLayer:
         prepool3s2: MaxPool3d((1,3,3), (1,2,2), (0,1,1)) over the INPUT
         first, the output at the pooled positions (FAC_CONV_PREPOOL3S2:
         prepool3s2_ok)."""
-        n, d, h, w, c = x.shape
-        if c != self.cin_p or x.dtype != TORCH16[self.dtype] or not x.is_contiguous():
-            raise ValueError(f"conv input must be contiguous {self.dtype} [N,D,H,W,{self.cin_p}], got "
-                             f"{x.dtype} {tuple(x.shape)}")
-        od, oh, ow = self.out_dims(d, h, w)
+        n, d, h, w, _ = x.shape
+        dsc = _desc(self, x, None, (RELU if relu else 0) | (RELU2 if relu2 else 0) | (OUT_F32 if out_f32 else 0) |
+                    (MAXPOOL3S2 if maxpool3s2 else 0) | (MAXPOOL3S1 if maxpool3s1 else 0) |
+                    (PREPOOL3S2 if prepool3s2 else 0))
+        od, oh, ow = dsc.od, dsc.oh, dsc.ow
         if prepool3s2:
             if not self.prepool3s2_ok(x) or residual is not None or relu2 or out_f32 or maxpool3s2 or maxpool3s1:
                 raise ValueError("prepool3s2 needs a 1x1x1 64 -> 64 conv on a 56-wide map, no residual / relu2 / "
@@ -241,48 +241,45 @@ class ConvLayer:
                                            out.data_ptr(), n * d, h, self.cin, self.cout, 0, 1 if relu else 0,
                                            _zero256(x.device).data_ptr(), _stream(x)), None, "fac_conv3x3")
                 return out
-        g = self.g
-        dsc = ConvDesc()
-        dsc.dtype = _lib.DTYPES[self.dtype]
-        dsc.inp = x.data_ptr()
-        dsc.n, dsc.d, dsc.h, dsc.w, dsc.cin = n, d, h, w, c
-        dsc.weight, dsc.bias = self.w.data_ptr(), self.b.data_ptr()
-        dsc.cout, dsc.k_pad = self.cout, self.k_pad
-        dsc.kd, dsc.kh, dsc.kw, dsc.sd, dsc.sh, dsc.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
-        dsc.pd, dsc.ph, dsc.pw = g.pd, g.ph, g.pw
+        # what differs from the plain descriptor: the output found above (the
+        # conv's own positions, before the fused pool, for maxpool3s2), the residual
         dsc.od, dsc.oh, dsc.ow = (od, 2 * oh, 2 * ow) if maxpool3s2 else (od, oh, ow)
         dsc.out, dsc.ldo, dsc.c_off = out.data_ptr(), out.shape[4], c_off
-        flags = (RELU if relu else 0) | (RELU2 if relu2 else 0) | (OUT_F32 if out_f32 else 0) | \
-            (MAXPOOL3S2 if maxpool3s2 else 0) | (MAXPOOL3S1 if maxpool3s1 else 0) | \
-            (PREPOOL3S2 if prepool3s2 else 0)
         if residual is not None:
             if tuple(residual.shape[:4]) != (n, od, oh, ow) or residual.dtype != x.dtype:
                 raise ValueError("residual must match the output positions and dtype")
             dsc.residual, dsc.ldr, dsc.r_off = residual.data_ptr(), residual.shape[4], 0
-            flags |= RESID
-        dsc.flags = flags
+            dsc.flags |= RESID
         _lib.check(_lib.load().fac_conv_nd(ctypes.byref(dsc), _stream(x)), None, "fac_conv_nd")
         return out
 
 
-def _desc(layer: ConvLayer, x: torch.Tensor, out: torch.Tensor | None, flags: int) -> "ConvDesc":
-    n, d, h, w, c = x.shape
-    if c != layer.cin_p or x.dtype != TORCH16[layer.dtype] or not x.is_contiguous():
-        raise ValueError(f"conv input must be contiguous {layer.dtype} [N,D,H,W,{layer.cin_p}], got "
-                         f"{x.dtype} {tuple(x.shape)}")
-    od, oh, ow = layer.out_dims(d, h, w)
+def _desc(layer: ConvLayer, x, out: torch.Tensor | None, flags: int, *, c_off: int = 0) -> "ConvDesc":
+    """The one place that fills a fac_conv_desc: `layer` over `x`, into
+    channels [c_off, c_off + cout) of `out` (None: no output of its own, or
+    set by the caller).  `x` is the input tensor, checked here, or the
+    (n, d, h, w) of an input the kernel makes itself (from a clip, or from
+    the conv before it in a fused pair)."""
+    if isinstance(x, torch.Tensor):
+        n, d, h, w, c = x.shape
+        if c != layer.cin_p or x.dtype != TORCH16[layer.dtype] or not x.is_contiguous():
+            raise ValueError(f"conv input must be contiguous {layer.dtype} [N,D,H,W,{layer.cin_p}], got "
+                             f"{x.dtype} {tuple(x.shape)}")
+    else:
+        n, d, h, w = x
     g = layer.g
     dsc = ConvDesc()
     dsc.dtype = _lib.DTYPES[layer.dtype]
-    dsc.inp = x.data_ptr()
-    dsc.n, dsc.d, dsc.h, dsc.w, dsc.cin = n, d, h, w, c
+    if isinstance(x, torch.Tensor):
+        dsc.inp = x.data_ptr()
+    dsc.n, dsc.d, dsc.h, dsc.w, dsc.cin = n, d, h, w, layer.cin_p
     dsc.weight, dsc.bias = layer.w.data_ptr(), layer.b.data_ptr()
     dsc.cout, dsc.k_pad = layer.cout, layer.k_pad
     dsc.kd, dsc.kh, dsc.kw, dsc.sd, dsc.sh, dsc.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
     dsc.pd, dsc.ph, dsc.pw = g.pd, g.ph, g.pw
-    dsc.od, dsc.oh, dsc.ow = od, oh, ow
+    dsc.od, dsc.oh, dsc.ow = layer.out_dims(d, h, w)
     if out is not None:
-        dsc.out, dsc.ldo, dsc.c_off = out.data_ptr(), out.shape[4], 0
+        dsc.out, dsc.ldo, dsc.c_off = out.data_ptr(), out.shape[4], c_off
     dsc.flags = flags
     return dsc
 
@@ -334,25 +331,10 @@ def conv_split(layer: ConvLayer, x: torch.Tensor, splits, out0: torch.Tensor, c_
     output channels): columns [0, s1) -> out0[..., c_off0:], [s1, s2) -> out1,
     [s2, cout) -> out2 (each [N,D,H,W,C] contiguous)."""
     s1, s2 = splits
-    n, d, h, w, c = x.shape
-    if c != layer.cin_p or x.dtype != TORCH16[layer.dtype] or not x.is_contiguous():
-        raise ValueError("conv_split input must be a contiguous 16-bit [N,D,H,W,cin] tensor")
-    od, oh, ow = layer.out_dims(d, h, w)
+    dsc = _desc(layer, x, out0, RELU if relu else 0, c_off=c_off0)
     for t, width in ((out1, s2 - s1), (out2, layer.cout - s2)):
-        if tuple(t.shape[:4]) != (n, od, oh, ow) or t.shape[4] < width or not t.is_contiguous():
+        if tuple(t.shape[:4]) != (dsc.n, dsc.od, dsc.oh, dsc.ow) or t.shape[4] < width or not t.is_contiguous():
             raise ValueError("conv_split outputs must be contiguous [N,D,H,W,C] tensors wide enough")
-    g = layer.g
-    dsc = ConvDesc()
-    dsc.dtype = _lib.DTYPES[layer.dtype]
-    dsc.inp = x.data_ptr()
-    dsc.n, dsc.d, dsc.h, dsc.w, dsc.cin = n, d, h, w, c
-    dsc.weight, dsc.bias = layer.w.data_ptr(), layer.b.data_ptr()
-    dsc.cout, dsc.k_pad = layer.cout, layer.k_pad
-    dsc.kd, dsc.kh, dsc.kw, dsc.sd, dsc.sh, dsc.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
-    dsc.pd, dsc.ph, dsc.pw = g.pd, g.ph, g.pw
-    dsc.od, dsc.oh, dsc.ow = od, oh, ow
-    dsc.out, dsc.ldo, dsc.c_off = out0.data_ptr(), out0.shape[4], c_off0
-    dsc.flags = RELU if relu else 0
     _lib.check(_lib.load().fac_conv_nd_split(ctypes.byref(dsc), out1.data_ptr(), out1.shape[4], s1, out2.data_ptr(),
                                              out2.shape[4], s2, _stream(x)), None, "fac_conv_nd_split")
 
@@ -452,19 +434,8 @@ def conv_s2d4_clip(layer: ConvLayer, clip: torch.Tensor, *, pad_before: int = 2,
         raise ValueError(f"expected a contiguous fp32 / uint8 clip [N,3,T,H,W], got {clip.dtype} {tuple(clip.shape)}")
     n, _, t, h, w = clip.shape
     hc, wc = h // 2 + pad_before + pad_after, w // 2 + pad_before + pad_after
-    od, oh, ow = layer.out_dims(t, hc, wc)
-    out = torch.empty(n, od, oh, ow, layer.cout, device=clip.device, dtype=TORCH16[layer.dtype])
-    g = layer.g
-    dsc = ConvDesc()
-    dsc.dtype = _lib.DTYPES[layer.dtype]
-    dsc.n, dsc.d, dsc.h, dsc.w, dsc.cin = n, t, hc, wc, layer.cin_p
-    dsc.weight, dsc.bias = layer.w.data_ptr(), layer.b.data_ptr()
-    dsc.cout, dsc.k_pad = layer.cout, layer.k_pad
-    dsc.kd, dsc.kh, dsc.kw, dsc.sd, dsc.sh, dsc.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
-    dsc.pd, dsc.ph, dsc.pw = g.pd, g.ph, g.pw
-    dsc.od, dsc.oh, dsc.ow = od, oh, ow
-    dsc.out, dsc.ldo, dsc.c_off = out.data_ptr(), layer.cout, 0
-    dsc.flags = RELU if relu else 0
+    out = torch.empty(n, *layer.out_dims(t, hc, wc), layer.cout, device=clip.device, dtype=TORCH16[layer.dtype])
+    dsc = _desc(layer, (n, t, hc, wc), out, RELU if relu else 0)   # the cells the kernel makes of the clip
     fn = "fac_conv_s2d4_clip_u8" if clip.dtype == torch.uint8 else "fac_conv_s2d4_clip"
     _lib.check(getattr(_lib.load(), fn)(ctypes.byref(dsc), clip.data_ptr(), h, w, pad_before, _stream(clip)), None, fn)
     return out
@@ -506,18 +477,7 @@ def sep_tiny(spatial: ConvLayer, temporal: ConvLayer, x: torch.Tensor, out: torc
     if tuple(out.shape[:4]) != tuple(x.shape[:4]) or not out.is_contiguous():
         raise ValueError("out must be contiguous [N,8,14,14,C]")
     sd = _desc(spatial, x, None, RELU)
-    n = x.shape[0]
-    td = ConvDesc()
-    td.dtype = _lib.DTYPES[temporal.dtype]
-    td.n, td.d, td.h, td.w, td.cin = n, 8, 14, 14, temporal.cin_p
-    td.weight, td.bias = temporal.w.data_ptr(), temporal.b.data_ptr()
-    td.cout, td.k_pad = temporal.cout, temporal.k_pad
-    g = temporal.g
-    td.kd, td.kh, td.kw, td.sd, td.sh, td.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
-    td.pd, td.ph, td.pw = g.pd, g.ph, g.pw
-    td.od, td.oh, td.ow = temporal.out_dims(8, 14, 14)
-    td.out, td.ldo, td.c_off = out.data_ptr(), out.shape[4], c_off
-    td.flags = RELU
+    td = _desc(temporal, (x.shape[0], 8, 14, 14), out, RELU, c_off=c_off)   # over the spatial half's map in LDS
     fn = "fac_sep_mid" if mid else "fac_sep_tiny"
     _lib.check(getattr(_lib.load(), fn)(ctypes.byref(sd), ctypes.byref(td), _stream(x)), None, fn)
     return out
@@ -533,30 +493,12 @@ def s3d_base0_u8(spatial: ConvLayer, temporal: ConvLayer, clip: torch.Tensor, *,
         raise ValueError(f"expected a contiguous uint8 clip [N,3,16,H,W], got {clip.dtype} {tuple(clip.shape)}")
     n, _, t, h, w = clip.shape
     hc, wc = h // 2 + pad_before + pad_after, w // 2 + pad_before + pad_after
-    od, oh, ow = spatial.out_dims(t, hc, wc)
-    g = spatial.g
-    sd = ConvDesc()
-    sd.dtype = _lib.DTYPES[spatial.dtype]
-    sd.n, sd.d, sd.h, sd.w, sd.cin = n, t, hc, wc, spatial.cin_p
-    sd.weight, sd.bias = spatial.w.data_ptr(), spatial.b.data_ptr()
-    sd.cout, sd.k_pad = spatial.cout, spatial.k_pad
-    sd.kd, sd.kh, sd.kw, sd.sd, sd.sh, sd.sw = g.kd, g.kh, g.kw, g.sd, g.sh, g.sw
-    sd.pd, sd.ph, sd.pw = g.pd, g.ph, g.pw
-    sd.od, sd.oh, sd.ow = od, oh, ow
-    sd.ldo, sd.flags = spatial.cout, RELU
-    tod, toh, tow = temporal.out_dims(od, oh, ow)
-    out = torch.empty(n, tod, toh, tow, temporal.cout, device=clip.device, dtype=TORCH16[temporal.dtype])
-    tg = temporal.g
-    td = ConvDesc()
-    td.dtype = _lib.DTYPES[temporal.dtype]
-    td.n, td.d, td.h, td.w, td.cin = n, od, oh, ow, temporal.cin_p
-    td.weight, td.bias = temporal.w.data_ptr(), temporal.b.data_ptr()
-    td.cout, td.k_pad = temporal.cout, temporal.k_pad
-    td.kd, td.kh, td.kw, td.sd, td.sh, td.sw = tg.kd, tg.kh, tg.kw, tg.sd, tg.sh, tg.sw
-    td.pd, td.ph, td.pw = tg.pd, tg.ph, tg.pw
-    td.od, td.oh, td.ow = tod, toh, tow
-    td.out, td.ldo, td.c_off = out.data_ptr(), temporal.cout, 0
-    td.flags = RELU
+    sd = _desc(spatial, (n, t, hc, wc), None, RELU)   # the clip's cells in, its map (dense, kept in LDS) out
+    sd.ldo = spatial.cout
+    mid = (n, sd.od, sd.oh, sd.ow)
+    out = torch.empty(n, *temporal.out_dims(*mid[1:]), temporal.cout, device=clip.device,
+                      dtype=TORCH16[temporal.dtype])
+    td = _desc(temporal, mid, out, RELU)
     _lib.check(_lib.load().fac_s3d_base0_u8(ctypes.byref(sd), ctypes.byref(td), clip.data_ptr(), h, w, pad_before,
                                             _stream(clip)), None, "fac_s3d_base0_u8")
     return out

@@ -129,6 +129,18 @@ int fac_conv_nd_split(const fac_conv_desc* desc, void* out1, int ldo1, int split
  * DUAL. */
 int fac_conv_nd_dual(const fac_conv_desc* desc, const fac_conv_desc* ds, void* stream);
 
+/* The kernel family fac_conv_nd / fac_conv_nd_split would launch for this
+ * descriptor ("conv_pw", "pw_res", "conv_tk2", "convnd_pt", ...; the generic
+ * implicit GEMM with its tile and workgroups per CU, "convnd_igemm:128x64:3"),
+ * or NULL with *status set when the call would be rejected.  split1 = split2
+ * = INT_MAX asks about fac_conv_nd, anything else about fac_conv_nd_split
+ * into dense segments (ldo1 = split2 - split1, ldo2 = cout - split2).
+ * Launches nothing; pointers in the descriptor are only tested for NULL.
+ * The answers follow fac_set_option's process-wide A/B knobs. */
+const char* fac_conv_nd_route(const fac_conv_desc* desc, int split1, int split2, int* status);
+/* The same for fac_conv_nd_dual and, below, fac_pool_nd. */
+const char* fac_conv_nd_dual_route(const fac_conv_desc* desc, const fac_conv_desc* ds, int* status);
+
 /* A ResNet-50 layer1 / layer2 bottleneck's conv3 and the next block's conv1
  * in one launch (ResVitKan.py:146-152; torchvision resnet50): c3 = the 1x1
  * 64 -> 256 (layer1) or 128 -> 512 (layer2) conv3 + bn3 with flags exactly
@@ -183,6 +195,7 @@ typedef struct fac_pool_desc {
 } fac_pool_desc;
 
 int fac_pool_nd(const fac_pool_desc* desc, void* stream);
+const char* fac_pool_nd_route(const fac_pool_desc* desc, int* status);
 
 /* Input staging: 3-channel images -> 16-bit channels-last with c_pad
  * channels (zeros beyond 3): out[n][s][c] = (x / div - mean[c]) / std[c]
