@@ -38,7 +38,11 @@ def _flags():
 # Per-file extra flags.  stem224.hip: no wave-level atomic aggregation, whose
 # prefix-sum code needs the box-claim atomic's return value at once (an
 # s_waitcnt vmcnt(0) at every box start); plain, its wait sits at the use.
-FILE_FLAGS: dict = {"stem224.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+# clip.hip: no FMA contraction.  The _rn intrinsics of its bicubic taps are
+# plain operators in the HIP headers, which hipcc's default -ffp-contract=fast
+# fuses once they are inlined; the taps must round like the host restatement's.
+FILE_FLAGS: dict = {"stem224.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+                    "clip.hip": ["-ffp-contract=off"]}
 
 
 def _headers_mtime() -> float:

@@ -52,6 +52,8 @@ hipError_t launch_video_score(const float* logits, int n, float* score, hipStrea
 hipError_t launch_video_score_seg(const float* logits, const int* seg, int nv, float* score, hipStream_t st);
 hipError_t launch_crop_resize(const uint8_t* frames, int n_frames, int H, int W, const int32_t* boxes, int n_boxes,
                               uint8_t* crops, hipStream_t st);
+hipError_t launch_clip_stage(const uint8_t* frames, int n_frames, int H, int W, const int32_t* boxes, int n_boxes,
+                             int T, uint8_t* clips, hipStream_t st);
 hipError_t launch_stem224(int dtype, bool u8, const void* in, const uint16_t* w1, const float* b1, const uint16_t* w2,
                           const float* b2, const uint16_t* w3, const float* b3, uint16_t* out, int B, int nwg,
                           hipStream_t s);
@@ -1308,6 +1310,20 @@ int fac_crop_resize_u8(const uint8_t* d_frames, int n_frames, int H, int W, cons
   if (!d_frames || !d_boxes || !d_crops || n_frames <= 0 || H <= 0 || W <= 0 || n_boxes < 0) return FAC_ERR_ARG;
   if ((long long)n_frames * H * W * 3 >= (1ll << 40)) return FAC_ERR_SHAPE;
   return fac::launch_crop_resize(d_frames, n_frames, H, W, d_boxes, n_boxes, d_crops, (hipStream_t)stream) ==
+                 hipSuccess
+             ? FAC_OK
+             : FAC_ERR_HIP;
+}
+
+int fac_clip_stage_u8(const uint8_t* d_frames, int n_frames, int H, int W, const int32_t* d_boxes, int n_boxes, int T,
+                      uint8_t* d_clips, void* stream) {
+  if (!d_frames || !d_boxes || !d_clips || n_frames <= 0 || H <= 0 || W <= 0 || n_boxes < 0 || T <= 0 ||
+      ((uintptr_t)d_clips & 3))  // (the kernel stores dwords)
+    return FAC_ERR_ARG;
+  // (under two pixels: the kernel's dword loads of 3-byte pixels need 4 bytes of frames)
+  if (n_boxes % T != 0 || (long long)n_frames * H * W * 3 >= (1ll << 40) || (long long)n_frames * H * W < 2)
+    return FAC_ERR_SHAPE;
+  return fac::launch_clip_stage(d_frames, n_frames, H, W, d_boxes, n_boxes, T, d_clips, (hipStream_t)stream) ==
                  hipSuccess
              ? FAC_OK
              : FAC_ERR_HIP;

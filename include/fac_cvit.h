@@ -186,6 +186,24 @@ int fac_video_score_seg(const float* d_logits, const int* d_seg, int nv, float* 
 int fac_crop_resize_u8(const uint8_t* d_frames, int n_frames, int H, int W, const int32_t* d_boxes, int n_boxes,
                        uint8_t* d_crops, void* stream);
 
+/* Clip staging of the S3D-family models (preprocessing/extract_crops.py:69,
+ * S3D-test.py:65-73,94-96, transforms/albu.py:9-26): for each row
+ * (frame, left, top, right, bottom, ow, oh) of d_boxes (int32 [n_boxes][7]),
+ * take frame[top:bottom, left:right] (clipped to the frame: cw x ch) of the
+ * BGR uint8 frames [n_frames][H][W][3], resize it to ow x oh -- a copy when
+ * max(cw, ch) == 224, cv2.INTER_AREA's area weights in exact integers when it
+ * is larger, cv2.INTER_CUBIC's 8-bit fixed-point scheme when it is smaller
+ * (csrc/clip.hip) -- and centre it in zero 224 x 224 planes (the odd pixel
+ * bottom / right, PadIfNeeded's) of d_clips, uint8 planar
+ * [n_boxes / T][3][T][224][224], channels still BGR: box i is frame i % T of
+ * clip i / T, the clip layout the S3D models take.  ow and oh (<= 224) come
+ * from the caller as IsotropicResize computes them (fac_fake_amd/clip.py
+ * box_table).  A bad frame index or an empty box, ow or oh gives zero
+ * planes; every byte of d_clips is written.  n_boxes must be a multiple of T
+ * and d_clips 4-byte aligned; the frames hold at least two pixels. */
+int fac_clip_stage_u8(const uint8_t* d_frames, int n_frames, int H, int W, const int32_t* d_boxes, int n_boxes, int T,
+                      uint8_t* d_clips, void* stream);
+
 /* Tuning knob: run the conv stem in sub-batches of `crops` crops (0 = whole
  * batch), so intermediate activations stay resident in the Infinity Cache. */
 int fac_set_stem_chunk(fac_ctx* ctx, int crops);
