@@ -4952,6 +4952,8 @@ int fac_kan_linear(const float* x, int rows, int in_f, int out_f, const float* g
   if (!x || !grid || !wcat || !y || !partial || rows <= 0 || in_f <= 0 || out_f <= 0) return FAC_ERR_ARG;
   if (n_knots != kKanNK) return FAC_ERR_SHAPE;  // grid_size 5, spline_order 3 (kan.py:21-22)
   const int chunks = (in_f + kKanIn - 1) / kKanIn;
+  // kan_reduce indexes the rows * out_f outputs, and the launches size their grids, in 32 bits
+  if ((long long)chunks * rows * out_f >= (1LL << 31)) return FAC_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   kan_partial<<<dim3(chunks, (rows + kKanRows - 1) / kKanRows), 256, 0, st>>>(x, rows, in_f, out_f, grid, wcat,
                                                                               (float*)partial);
@@ -4968,14 +4970,14 @@ int fac_sigmoid(const float* x, float* y, int n, void* stream) {
 
 int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
              const float* bn4, const float* w2, const float* b2, void* out, void* stream) {
-  if (!x || !out || !w1 || !b1 || !bn4 || !w2 || !b2 || n <= 0 || h <= 0 || w <= 0 || groups <= 0 || c % groups)
+  if (!x || !out || !w1 || !b1 || !bn4 || !w2 || !b2 || n <= 0 || h <= 0 || w <= 0 || c <= 0 || groups <= 0 ||
+      c % groups || !fac::dtype_ok(dtype))
     return FAC_ERR_ARG;
   const int cg = c / groups;
   if (h > 16 || w > 16 || cg % 16 || cg > 256 || h * w * cg > 16384 || (2 * h + 2 * w) * cg > 8192 ||
       (2 * h + 2 * w) > 64)
     return FAC_ERR_SHAPE;
-  // (any dtype but bf16 runs as fp16)
-  return fac::with_dtype(dtype == FAC_DTYPE_BF16 ? FAC_DTYPE_BF16 : FAC_DTYPE_F16, [&](auto t) {
+  return fac::with_dtype(dtype, [&](auto t) {
     fac::ggca_k<decltype(t)><<<n * groups, 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, h, w, c, groups, w1, b1,
                                                                           bn4, w2, b2, (uint16_t*)out);
   });

@@ -339,8 +339,8 @@ def conv_split(layer: ConvLayer, x: torch.Tensor, splits, out0: torch.Tensor, c_
                                              out2.shape[4], s2, _stream(x)), None, "fac_conv_nd_split")
 
 
-def pool(x: torch.Tensor, kernel, stride, padding=0, mode: str = "max", out: torch.Tensor | None = None,
-         c_off: int = 0) -> torch.Tensor:
+def _pool_desc(x: torch.Tensor, kernel, stride, padding, mode: str, out: torch.Tensor | None, c_off: int):
+    """The one place that fills a fac_pool_desc: (desc, out), `out` allocated when None."""
     n, d, h, w, c = x.shape
     (kd, kh, kw), (sd, sh, sw), (pd, ph, pw) = _triple(kernel), _triple(stride), _pads(padding)
     od, oh, ow = (d + 2 * pd - kd) // sd + 1, (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
@@ -354,8 +354,26 @@ def pool(x: torch.Tensor, kernel, stride, padding=0, mode: str = "max", out: tor
     dsc.od, dsc.oh, dsc.ow = od, oh, ow
     dsc.mode = {"max": 0, "avg": 1}[mode]
     dsc.out, dsc.ldo, dsc.c_off = out.data_ptr(), out.shape[4], c_off
+    return dsc, out
+
+
+def pool(x: torch.Tensor, kernel, stride, padding=0, mode: str = "max", out: torch.Tensor | None = None,
+         c_off: int = 0) -> torch.Tensor:
+    dsc, out = _pool_desc(x, kernel, stride, padding, mode, out, c_off)
     _lib.check(_lib.load().fac_pool_nd(ctypes.byref(dsc), _stream(x)), None, "fac_pool_nd")
     return out
+
+
+def pool_route(x: torch.Tensor, kernel, stride, padding=0, mode: str = "max", out: torch.Tensor | None = None,
+               c_off: int = 0) -> str:
+    """The kernel family ``pool`` would launch for these arguments (fac_pool_nd_route: "pool_nd",
+    "pool_max_win", "maxpool3_s1", ...); launches nothing, raises where ``pool`` would be refused."""
+    dsc, _ = _pool_desc(x, kernel, stride, padding, mode, out, c_off)
+    st = ctypes.c_int(0)
+    name = _lib.load().fac_pool_nd_route(ctypes.byref(dsc), ctypes.byref(st))
+    if not name:
+        _lib.check(st.value, None, "fac_pool_nd_route")
+    return name.decode()
 
 
 def max_pool_sep(x: torch.Tensor, kernel, stride, padding=0) -> torch.Tensor:
@@ -381,35 +399,47 @@ def max_pool_sep(x: torch.Tensor, kernel, stride, padding=0) -> torch.Tensor:
     return y if y is not x else pool(x, kernel, stride, padding, "max")
 
 
+def _pack_out(out: torch.Tensor | None, shape, device, dtype: str) -> torch.Tensor:
+    """The packers' output: a new tensor, or the caller's if it is exactly what a new one would be."""
+    if out is None:
+        return torch.empty(*shape, device=device, dtype=TORCH16[dtype])
+    if tuple(out.shape) != tuple(shape) or out.dtype != TORCH16[dtype] or out.device != device or \
+            not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError(f"out must be a contiguous 16-byte aligned {dtype} tensor {tuple(shape)} on {device}")
+    return out
+
+
 def pack_input(src: torch.Tensor, *, dtype: str, u8: bool, div: float = 1.0, mean=None, std=None,
-               spatial: tuple[int, ...]) -> torch.Tensor:
-    """3-channel images -> 16-bit [N, D, H, W, 8] (fac_pack_input).
-    u8: src uint8 [N, *spatial, 3]; else fp32 planar [N, 3, *spatial]."""
+               spatial: tuple[int, ...], c_pad: int = 8, out: torch.Tensor | None = None) -> torch.Tensor:
+    """3-channel images -> 16-bit [N, D, H, W, c_pad] (fac_pack_input), zeros
+    beyond channel 3; c_pad a multiple of 8.  u8: src uint8 [N, *spatial, 3];
+    else fp32 planar [N, 3, *spatial].  out: a contiguous tensor of that shape
+    and type to write instead of a new one."""
     n = src.shape[0]
     s = 1
     for v in spatial:
         s *= v
     d, h, w = (1,) * (3 - len(spatial)) + tuple(spatial)
-    out = torch.empty(n, d, h, w, 8, device=src.device, dtype=TORCH16[dtype])
+    out = _pack_out(out, (n, d, h, w, c_pad), src.device, dtype)
     m = (ctypes.c_float * 3)(*(mean if mean is not None else (0.0, 0.0, 0.0)))
     sd = (ctypes.c_float * 3)(*(std if std is not None else (1.0, 1.0, 1.0)))
     src = src.contiguous()
     _lib.check(_lib.load().fac_pack_input(_lib.DTYPES[dtype], src.data_ptr(), 0 if u8 else 1, n, s, float(div),
                                           ctypes.cast(m, ctypes.c_void_p), ctypes.cast(sd, ctypes.c_void_p),
-                                          out.data_ptr(), 8, _stream(src)), None, "fac_pack_input")
+                                          out.data_ptr(), c_pad, _stream(src)), None, "fac_pack_input")
     return out
 
 
 def pack_input_s2d(src: torch.Tensor, *, dtype: str, u8: bool, div: float = 1.0, mean=None, std=None,
-                   pad_before: int = 2, pad_after: int = 1) -> torch.Tensor:
+                   pad_before: int = 2, pad_after: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
     """3-channel images -> 16-bit space-to-depth cells [N, T, h/2+pb+pa, w/2+pb+pa, 16]
     (fac_pack_input_s2d).  u8: src uint8 [N, h, w, 3] (T = 1); else fp32
-    [N, 3, h, w] (T = 1) or a clip batch [N, 3, T, h, w]."""
+    [N, 3, h, w] (T = 1) or a clip batch [N, 3, T, h, w].  out: as in pack_input."""
     n = src.shape[0]
     frames = src.shape[2] if (not u8 and src.dim() == 5) else 1
     h, w = (src.shape[1], src.shape[2]) if u8 else (src.shape[-2], src.shape[-1])
     ho, wo = h // 2 + pad_before + pad_after, w // 2 + pad_before + pad_after
-    out = torch.empty(n, frames, ho, wo, 16, device=src.device, dtype=TORCH16[dtype])
+    out = _pack_out(out, (n, frames, ho, wo, 16), src.device, dtype)
     m = (ctypes.c_float * 3)(*(mean if mean is not None else (0.0, 0.0, 0.0)))
     sd = (ctypes.c_float * 3)(*(std if std is not None else (1.0, 1.0, 1.0)))
     src = src.contiguous()

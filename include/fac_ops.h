@@ -256,7 +256,10 @@ int fac_s3d_base0_u8(const fac_conv_desc* sdesc, const fac_conv_desc* tdesc, con
  * [in][1 + nb][out] (index 0 = base_weight[o][i], 1.. = the scaled spline
  * weights spline_weight[o][i][k] * spline_scaler[o][i], nb = n_knots - 4).
  * x [rows][in] fp32 -> y [rows][out] fp32.  `partial` is a scratch buffer of
- * fac_kan_scratch_bytes() bytes. */
+ * fac_kan_scratch_bytes() bytes: ceil(in/32) slabs of [rows][out] fp32
+ * (0 for a size <= 0).  FAC_ERR_ARG: a null pointer or a size <= 0;
+ * FAC_ERR_SHAPE: n_knots != 12, or ceil(in/32)*rows*out >= 2^31 (the
+ * outputs and the slabs are indexed in 32 bits). */
 int fac_kan_linear(const float* x, int rows, int in_f, int out_f, const float* grid, int n_knots, const float* wcat,
                    float* y, void* partial, void* stream);
 size_t fac_kan_scratch_bytes(int rows, int in_f, int out_f);
@@ -270,7 +273,10 @@ size_t fac_kan_scratch_bytes(int rows, int in_f, int out_f);
  *   out = x * ((x * att_h) * att_w), fp32 arithmetic, 16-bit out.
  * w1 [cr][cg], b1 [cr], bn4 [4][cr] = running_mean, running_var, weight,
  * bias; w2 [cg][cr], b2 [cg] (fp32; cg = c/groups, cr = cg/16).
- * h, w <= 16, cg a multiple of 16, h*w*cg <= 16384. */
+ * FAC_ERR_SHAPE unless h, w <= 16, cg a multiple of 16, cg <= 256,
+ * h*w*cg <= 16384 and (2h + 2w)*cg <= 8192 (the group's features and its
+ * 2h + 2w pooled vectors are held in LDS).  FAC_ERR_ARG: a null pointer, a
+ * dtype other than bf16 / fp16, n, h, w, c or groups <= 0, c % groups != 0. */
 int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
              const float* bn4, const float* w2, const float* b2, void* out, void* stream);
 
