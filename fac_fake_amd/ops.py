@@ -831,6 +831,63 @@ def bn_max_pool(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, kt: i
     return out
 
 
+class Conv3x3Res:
+    """A ResNet BasicBlock's second conv packed for fac_conv3x3_res (resnet.hip):
+    Conv2d(3x3, stride 1, padding 1, c -> c) + folded BN, + residual, ReLU, on
+    one of a ResNet-34's maps, (h, c) in SHAPES.  weight: the folded fp32
+    [c, c, 3, 3]; bias fp32 [c]."""
+
+    SHAPES = ((56, 64), (28, 128), (14, 256), (7, 512))
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, h: int, *, dtype: str, device):
+        w = weight.detach().to("cpu", torch.float32).contiguous()
+        c = int(w.shape[0])
+        if tuple(w.shape) != (c, c, 3, 3):
+            raise ValueError(f"Conv3x3Res: weight must be [c,c,3,3], got {tuple(w.shape)}")
+        lib = _lib.load()
+        n = lib.fac_conv3x3_res_packed_elems(h, c)
+        if not n:
+            raise ValueError(f"Conv3x3Res: no fac_conv3x3_res kernel for a {h}x{h}x{c} map (has {self.SHAPES})")
+        pk = torch.empty(n, dtype=torch.int16)
+        _lib.check(lib.fac_conv3x3_res_pack(_lib.DTYPES[dtype], h, c, w.data_ptr(), pk.data_ptr()), None,
+                   "fac_conv3x3_res_pack")
+        self.h, self.c, self.dtype = h, c, dtype
+        self.w = pk.view(TORCH16[dtype]).to(device)
+        self.b = bias.detach().to("cpu", torch.float32).contiguous().to(device)
+
+    def __call__(self, x: torch.Tensor, residual: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        want = (self.h, self.h, self.c)
+        for t, what in ((x, "input"), (residual, "residual")):
+            if tuple(t.shape[-3:]) != want or t.dtype != TORCH16[self.dtype] or not t.is_contiguous() or \
+                    t.shape != x.shape or not t.is_cuda:
+                raise ValueError(f"Conv3x3Res: {what} must be a contiguous {self.dtype} GPU tensor [N,...,{self.h},"
+                                 f"{self.h},{self.c}], got {t.dtype} {tuple(t.shape)}")
+        if out is None:
+            out = torch.empty_like(x)
+        if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("Conv3x3Res: out must match the input in shape, dtype, device and be contiguous")
+        n = x.numel() // (self.h * self.h * self.c)
+        _lib.check(_lib.load().fac_conv3x3_res(_lib.DTYPES[self.dtype], x.data_ptr(), self.w.data_ptr(),
+                                               self.b.data_ptr(), residual.data_ptr(), out.data_ptr(), n, self.h,
+                                               self.c, _stream(x)), None, "fac_conv3x3_res")
+        return out
+
+
+def avgpool_f32(x: torch.Tensor) -> torch.Tensor:
+    """Mean over every position of a 16-bit channels-last map [N, ..., C] ->
+    fp32 [N, C] (fac_avgpool_f32): fp32 sums in a fixed order, the result never
+    rounded to 16 bits."""
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.dim() < 2 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"avgpool_f32: expected a contiguous 16-bit GPU tensor [N,...,C], got {x.dtype} "
+                         f"{tuple(x.shape)}")
+    n, c = int(x.shape[0]), int(x.shape[-1])
+    s = x.numel() // max(n * c, 1)
+    y = torch.empty(n, c, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().fac_avgpool_f32(0 if x.dtype == torch.bfloat16 else 1, x.data_ptr(), n, s, c, y.data_ptr(),
+                                           _stream(x)), None, "fac_avgpool_f32")
+    return y
+
+
 def sigmoid(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty_like(x)
     _lib.check(_lib.load().fac_sigmoid(x.data_ptr(), y.data_ptr(), x.numel(), _stream(x)), None, "fac_sigmoid")

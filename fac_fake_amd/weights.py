@@ -269,6 +269,100 @@ def _synthetic(name, shape, kind, seed):
     return _u(name, shape, seed, lo, hi)
 
 
+# ---------------------------------------------------------------- ResKan
+# CViT-main/ResKan/kan_resnet.py::resnet34 (:132-260): ResNet-34 of BasicBlocks
+# [3,4,6,3] (:11-65: conv3x3 + bn1 + ReLU, conv3x3 + bn2, + identity, ReLU),
+# global average pool, KAN([512, 64, num_classes]).
+RESNET34_LAYERS = [(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)]  # (channels, blocks, stride)
+
+
+def resnet34_blocks():
+    """(prefix, in channels, channels, stride, has_downsample) per BasicBlock,
+    in _make_layer order (kan_resnet.py:188-223)."""
+    out, inp = [], 64
+    for li, (ch, blocks, stride) in enumerate(RESNET34_LAYERS):
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            out.append((f"layer{li + 1}.{b}", inp, ch, s, b == 0 and (s != 1 or inp != ch)))
+            inp = ch
+    return out
+
+
+def reskan_param_specs(num_classes=2):
+    """(name, shape, kind) for every key of kan_resnet.resnet34's state_dict
+    (include_top=False, include_top_kan=True), in its order (224 keys)."""
+    specs = [("conv1.weight", (64, 3, 7, 7), "conv")] + _bn_specs("bn1", 64)
+    for p, inp, ch, _s, ds in resnet34_blocks():
+        specs += [(f"{p}.conv1.weight", (ch, inp, 3, 3), "conv")] + _bn_specs(f"{p}.bn1", ch)
+        specs += [(f"{p}.conv2.weight", (ch, ch, 3, 3), "conv")] + _bn_specs(f"{p}.bn2", ch, "gamma_res")
+        if ds:
+            specs += [(f"{p}.downsample.0.weight", (ch, inp, 1, 1), "conv")] + _bn_specs(f"{p}.downsample.1", ch)
+    nb = KAN_GRID_SIZE + KAN_ORDER
+    for i, (fi, fo) in enumerate([(512, 64), (64, num_classes)]):
+        p = f"kan.layers.{i}"
+        specs += [(f"{p}.base_weight", (fo, fi), "kbase"), (f"{p}.spline_weight", (fo, fi, nb), "kspline"),
+                  (f"{p}.spline_scaler", (fo, fi), "kscaler"),
+                  (f"{p}.grid", (fi, KAN_GRID_SIZE + 2 * KAN_ORDER + 1), "kgrid")]
+    return specs
+
+
+def make_reskan_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic ResKan weights (same generator).  The convs are drawn at
+    +-sqrt(3 / fan_in) and every block's bn2 gets gamma 0.2..0.5, so the
+    residual stream of 16 standard (bn2 -> add -> ReLU) blocks ends with most
+    pooled features inside the KAN's knot span [-2.2, 2.2] and some beyond
+    its inner interval; the KAN's second layer is scaled up for O(1)
+    logits that differ between crops.  tools/make_golden_reskan.py asserts the
+    outcome on the fixture crops."""
+    sd = OrderedDict()
+    for name, shape, kind in reskan_param_specs(**kw):
+        if kind == "nbt":
+            sd[name] = np.array(0, dtype=np.int64)
+        elif kind == "conv":
+            a = float(np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "gamma_res":
+            sd[name] = _u(name, shape, seed, 0.2, 0.5)
+        elif kind == "kgrid":
+            sd[name] = kan_grid(shape[0])
+        elif kind in ("kbase", "kscaler"):
+            a = float((RESKAN_KAN_GAIN[1] if ".layers.1." in name else RESKAN_KAN_GAIN[0]) / np.sqrt(shape[1]))
+            sd[name] = _u(name, shape, seed, -a, a)
+        elif kind == "kspline":
+            sd[name] = _u(name, shape, seed, -0.5, 0.5)
+        else:
+            sd[name] = _synthetic(name, shape, kind, seed)
+    return sd
+
+
+# gains of the two KANLinear layers' base_weight / spline_scaler bounds over 1 / sqrt(in)
+RESKAN_KAN_GAIN = (1.0, 8.0)
+
+
+def reskan_crops_varied(n: int, seed: int, size: int = 224) -> np.ndarray:
+    """n uint8 NHWC crops [n, size, size, 3] that differ in content, not only
+    in noise: crop k is a low-frequency colour wave (per-crop direction,
+    frequency, phase, brightness and contrast, all on ``uniform``'s 2^-24
+    grid) blended with uniform noise at a per-crop weight.  A global average
+    pool averages uniform noise away, so ``make_crops`` gives every crop almost
+    the same pooled features; these spread them (as s3d_clips_varied does for
+    clips)."""
+    p = uniform("reskan_crop_params", n * 8, seed).astype(np.float64).reshape(n, 8)
+    noise = make_crops(n, seed, size).astype(np.float64)
+    yy = np.arange(size, dtype=np.float64)[:, None] / size
+    xx = np.arange(size, dtype=np.float64)[None, :] / size
+    out = np.empty((n, size, size, 3), np.uint8)
+    for k in range(n):
+        a, b, ph = 3 * p[k, 0], 3 * p[k, 1], np.pi * p[k, 2]
+        br, amp = 60 * p[k, 3], 60 + 50 * p[k, 4]
+        alpha = 0.15 + 0.7 * k / max(n - 1, 1)
+        for ch in range(3):
+            wave = 128 + br + amp * np.sin(2 * np.pi * (a * xx + b * yy) + ph + (2.1 + p[k, 5]) * ch)
+            v = (1 - alpha) * wave + alpha * noise[k, :, :, ch]
+            out[k, :, :, ch] = np.clip(np.rint(v), 0, 255).astype(np.uint8)
+    return out
+
+
 # ---------------------------------------------------------------- S3D
 # sx_exp_deepfakedetect-master/S3D/model.py: S3D(num_class, SRM_net) (:6-48)
 # with BasicConv3d / SepConv3d (:50-82, BatchNorm3d eps 1e-3) and the

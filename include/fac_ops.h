@@ -407,6 +407,30 @@ int fac_stem224_pack_conv1(int dtype, const float* w, uint16_t* out);
 int fac_stem224(int dtype, int u8, const void* in, const void* w1p, const float* b1, const void* w2, const float* b2,
                 const void* w3, const float* b3, void* out, int n, void* stream);
 
+/* A ResNet BasicBlock's second conv (CViT-main/ResKan/kan_resnet.py:57-63) in
+ * one launch (resnet.hip): Conv2d(3x3, stride 1, padding 1, c -> c) + folded
+ * bn2, + residual, then ReLU: out = max(conv(in) + bias + residual, 0).
+ * in, residual, out: 16-bit channels-last [n][h][h][c]; fp32 accumulation,
+ * the residual added in fp32, one rounding on the store.  (h, c) is one of a
+ * ResNet-34's maps: (56, 64), (28, 128), (14, 256), (7, 512); at 7 the GEMM
+ * rows run across crops (n*49), padding stays per crop.  wpk:
+ * fac_conv3x3_res_pack of the folded fp32 weight [c][c][3][3] (host -> host,
+ * fac_conv3x3_res_packed_elems 16-bit elements, 0 for an unsupported shape);
+ * bias fp32 [c].  A crop's output does not depend on n.
+ * FAC_ERR_ARG: a null pointer, a bad dtype, n <= 0; FAC_ERR_SHAPE: any other
+ * (h, c), or n * 14 >= 2^31 (the launch grid). */
+size_t fac_conv3x3_res_packed_elems(int h, int c);
+int fac_conv3x3_res_pack(int dtype, int h, int c, const float* w, uint16_t* out);
+int fac_conv3x3_res(int dtype, const void* in, const void* wpk, const float* bias, const void* residual, void* out,
+                    int n, int h, int c, void* stream);
+
+/* Mean over s of 16-bit x [n][s][c] -> fp32 y [n][c] (a global average pool
+ * whose result is not rounded to 16 bits: the input of a KAN head).  fp32
+ * sums over s in index order, no atomics: bitwise reproducible.  x 16-byte
+ * aligned.  FAC_ERR_ARG: a null pointer, a bad dtype, n <= 0; FAC_ERR_SHAPE:
+ * s < 1, c < 8 or c % 8 != 0. */
+int fac_avgpool_f32(int dtype, const void* x, int n, int s, int c, float* y, void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
