@@ -38,9 +38,6 @@ hipError_t launch_gemm(int dtype, int epi, const uint16_t* A, int lda, const uin
 hipError_t launch_embed_finalize_ln(int dtype, const float* slab, int S, int B, const float* bias, const float* cls,
                                     const float* pos, const int32_t* pidx, float* x, const float* g, const float* bt,
                                     uint16_t* y, int* err, int seq, hipStream_t st);
-hipError_t launch_layernorm(int dtype, const float* x, const float* g, const float* b, uint16_t* y, int R,
-                            hipStream_t st);
-hipError_t launch_gather_cls(int dtype, const float* x, uint16_t* c, int B, hipStream_t st);
 hipError_t launch_resid_layernorm(int dtype, float* x, const float* slab, int S, const float* bias, const float* g,
                                  const float* b, uint16_t* y, int R, hipStream_t st, float eps = 1e-5f);
 hipError_t launch_resid_cls(int dtype, const float* x, const float* slab, int S, const float* bias, uint16_t* c, int B,
@@ -1194,6 +1191,66 @@ int fac_debug_gemm(fac_ctx* c, int epi, const uint16_t* d_a, const uint16_t* d_w
   if (e != hipSuccess) return set_err(c, e == hipErrorInvalidValue ? FAC_ERR_ARG : FAC_ERR_HIP,
                                       std::string("debug_gemm: ") + hipGetErrorString(e));
   return FAC_OK;
+}
+
+// The encoder's row kernels alone, on the caller's buffers: exactly the
+// launches of tail_impl (only the context's dtype and device are used).
+static int debug_launched(fac_ctx* c, const char* what, hipError_t e) {
+  if (e != hipSuccess)
+    return set_err(c, e == hipErrorInvalidValue ? FAC_ERR_ARG : FAC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  return FAC_OK;
+}
+
+int fac_debug_embed_ln(fac_ctx* c, const float* d_slab, int S, int B, const float* d_bias, const float* d_cls,
+                       const float* d_pos, const int32_t* d_pidx, float* d_x, const float* d_g, const float* d_b,
+                       uint16_t* d_y, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!d_slab || !d_bias || !d_cls || !d_pos || !d_pidx || !d_x || !d_g || !d_b || !d_y || B <= 0 ||
+      (S != 7 && S != 14 && S != 28))
+    return set_err(c, FAC_ERR_ARG, "bad debug_embed_ln arguments (S must be 7, 14 or 28)");
+  DevGuard g(c->device);
+  // no error flag: an out-of-range slot clamps without marking the context
+  return debug_launched(c, "debug_embed_ln",
+                        fac::launch_embed_finalize_ln(c->dtype, d_slab, S, B, d_bias, d_cls, d_pos, d_pidx, d_x, d_g,
+                                                      d_b, d_y, nullptr, 0, (hipStream_t)stream));
+}
+
+int fac_debug_resid_ln(fac_ctx* c, float* d_x, const float* d_slab, int S, const float* d_bias, const float* d_g,
+                       const float* d_b, uint16_t* d_y, int R, float eps, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!d_x || !d_slab || !d_bias || !d_g || !d_b || !d_y || R <= 0 || (S != 1 && S != 2 && S != 4) || !(eps > 0.f))
+    return set_err(c, FAC_ERR_ARG, "bad debug_resid_ln arguments (S must be 1, 2 or 4)");
+  DevGuard g(c->device);
+  return debug_launched(c, "debug_resid_ln",
+                        fac::launch_resid_layernorm(c->dtype, d_x, d_slab, S, d_bias, d_g, d_b, d_y, R,
+                                                    (hipStream_t)stream, eps));
+}
+
+int fac_debug_resid_cls(fac_ctx* c, const float* d_x, const float* d_slab, int S, const float* d_bias, uint16_t* d_c,
+                        int B, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!d_x || !d_slab || !d_bias || !d_c || B <= 0 || (S != 1 && S != 2 && S != 4))
+    return set_err(c, FAC_ERR_ARG, "bad debug_resid_cls arguments (S must be 1, 2 or 4)");
+  DevGuard g(c->device);
+  return debug_launched(c, "debug_resid_cls",
+                        fac::launch_resid_cls(c->dtype, d_x, d_slab, S, d_bias, d_c, B, (hipStream_t)stream));
+}
+
+int fac_debug_attention(fac_ctx* c, const float* d_qkv, uint16_t* d_o, int B, float scale, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!d_qkv || !d_o || B <= 0) return set_err(c, FAC_ERR_ARG, "bad debug_attention arguments");
+  DevGuard g(c->device);
+  return debug_launched(c, "debug_attention",
+                        fac::launch_attention2(c->dtype, d_qkv, d_o, B, scale, (hipStream_t)stream));
+}
+
+int fac_debug_head_out(fac_ctx* c, const float* d_hid, const float* d_w2, const float* d_b2, float* d_logits,
+                       float* d_probs, int B, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!d_hid || !d_w2 || !d_b2 || !d_logits || B <= 0) return set_err(c, FAC_ERR_ARG, "bad debug_head_out arguments");
+  DevGuard g(c->device);
+  return debug_launched(c, "debug_head_out",
+                        fac::launch_head_out(d_hid, d_w2, d_b2, d_logits, d_probs, B, (hipStream_t)stream));
 }
 
 int fac_debug_features_u8(fac_ctx* c, const uint8_t* d_in, int B, int layer, uint16_t* d_out, void* stream) {

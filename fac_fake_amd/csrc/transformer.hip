@@ -226,20 +226,6 @@ __global__ __launch_bounds__(64) void embed_finalize_ln(const float* __restrict_
   ln_row_store<T>(v, g, bta, y + (size_t)r * 1024, lane);
 }
 
-// LayerNorm(1024, eps 1e-5) (PreNorm, cvit.py:13-20): one wave per row,
-// fp32 statistics, 16-bit output feeding the next GEMM.
-template <class T>
-__global__ __launch_bounds__(64) void layernorm_rows(const float* __restrict__ x, const float* __restrict__ g,
-                                                     const float* __restrict__ bta, uint16_t* __restrict__ y,
-                                                     int R) {
-  const int row = blockIdx.x, lane = threadIdx.x;
-  const float* xr = x + (size_t)row * 1024;
-  f32x4 v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = *(const f32x4*)(xr + i * 256 + lane * 4);
-  ln_row_store<T>(v, g, bta, y + (size_t)row * 1024, lane);
-}
-
 // Residual add of a split-K projection + the next PreNorm LayerNorm, fused:
 //   x[r] += (sum_s slab[s][r]) + bias      (Residual, cvit.py:10-11)
 //   y[r]  = LayerNorm(x[r]) * g + b -> 16-bit (PreNorm, cvit.py:19-20)
@@ -274,19 +260,6 @@ __global__ __launch_bounds__(256) void resid_cls(const float* __restrict__ x, co
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
   *(u16x4*)(c + (size_t)b * 1024 + col) = o;
-}
-
-// CLS rows of the fp32 residual stream -> 16-bit [B][1024] (cvit.py:177).
-template <class T>
-__global__ __launch_bounds__(256) void gather_cls(const float* __restrict__ x, uint16_t* __restrict__ c, int B) {
-  const int i = blockIdx.x * 256 + threadIdx.x;  // over B*256 float4 groups
-  if (i >= B * 256) return;
-  const int b = i >> 8, q = i & 255;
-  const f32x4 v = *(const f32x4*)(x + (size_t)(2 * b) * 1024 + q * 4);
-  u16x4 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = T::from_f32(v[j]);
-  *(u16x4*)(c + (size_t)b * 1024 + q * 4) = o;
 }
 
 // Attention core for n = 2 tokens, 8 heads x 128 (cvit.py:43-60):
@@ -551,13 +524,6 @@ hipError_t launch_embed_finalize_ln(int dtype, const float* slab, int S, int B, 
   return embed_ln_t<F16>(slab, S, B, bias, cls, pos, pidx, x, g, bt, y, err, seq, st);
 }
 
-hipError_t launch_layernorm(int dtype, const float* x, const float* g, const float* b, uint16_t* y, int R,
-                            hipStream_t st) {
-  if (dtype == 0) layernorm_rows<BF16><<<R, 64, 0, st>>>(x, g, b, y, R);
-  else layernorm_rows<F16><<<R, 64, 0, st>>>(x, g, b, y, R);
-  return hipGetLastError();
-}
-
 template <class T>
 static hipError_t resid_ln_t(float* x, const float* slab, int S, const float* bias, const float* g, const float* b,
                              uint16_t* y, int R, hipStream_t st, float eps) {
@@ -593,13 +559,6 @@ hipError_t launch_resid_cls(int dtype, const float* x, const float* slab, int S,
                             hipStream_t st) {
   if (dtype == 0) return resid_cls_t<BF16>(x, slab, S, bias, c, B, st);
   return resid_cls_t<F16>(x, slab, S, bias, c, B, st);
-}
-
-hipError_t launch_gather_cls(int dtype, const float* x, uint16_t* c, int B, hipStream_t st) {
-  dim3 grid(B);
-  if (dtype == 0) gather_cls<BF16><<<grid, 256, 0, st>>>(x, c, B);
-  else gather_cls<F16><<<grid, 256, 0, st>>>(x, c, B);
-  return hipGetLastError();
 }
 
 hipError_t launch_attention2(int dtype, const float* qkv, uint16_t* o, int B, float scale, hipStream_t st) {

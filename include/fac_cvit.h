@@ -135,7 +135,25 @@ int fac_pipeline_join(fac_ctx* ctx, int keep, void* stream);
  * row-major operands, fp32 accumulation) with epilogue `epi` (0 fp32 + bias,
  * 1 fp32 relu, 2 16-bit gelu, 3 fp32 residual +=, 4 split-K fp32 partial
  * slabs [splits][M][N], 5 16-bit + bias), tile `variant` (-1 default, 0..6):
- * the nn.Linear calls of cvit.py:28,39,50,164 in isolation. */
+ * the nn.Linear calls of cvit.py:28,39,50,164 in isolation.
+ * The encoder's row kernels between the GEMMs, each alone, stream-ordered, on
+ * the caller's device buffers (the context gives only the 16-bit type and the
+ * device; no weights need be loaded, no context buffer is touched); rows are
+ * 1024 wide, row 2b = CLS token of crop b, row 2b+1 = its patch token:
+ * fac_debug_embed_ln: x[2b] = cls + pos[p_b], x[2b+1] = sum_s slab[s][b] +
+ * bias + pos[p_b] (slab fp32 [S][B][1024], S = 7, 14 or 28; pos [32][1024];
+ * p_b = d_pos_index[b] clamped to [0,31], without raising the context's
+ * pos_index flag), x fp32 [2B][1024], y = LayerNorm(x; g, b, eps 1e-5) 16-bit.
+ * fac_debug_resid_ln: x[r] += sum_s slab[s][r] + bias (slab fp32
+ * [S][R][1024], S = 1, 2 or 4), y = LayerNorm(x; g, b, eps) 16-bit [R][1024].
+ * fac_debug_resid_cls: c[b] = x[2b] + sum_s slab[s][2b] + bias -> 16-bit
+ * [B][1024] (x and slab rows as for resid_ln with R = 2B; patch rows unread).
+ * fac_debug_attention: qkv fp32 [2B][3072] laid out (qkv h d), 8 heads x 128,
+ * softmax(q.k^T * scale) . v over each crop's two tokens -> 16-bit [2B][1024].
+ * fac_debug_head_out: logits[b] = hid[b] . w2^T + b2 (hid fp32 [B][2048], w2
+ * [2][2048]), probs = sigmoid(logits) unless d_probs is null.
+ * FAC_ERR_ARG for a null pointer (d_probs excepted), B or R <= 0, or an S not
+ * listed. */
 #define FAC_PROFILE_STAGES 20
 int fac_debug_features_u8(fac_ctx* ctx, const uint8_t* d_in, int B, int layer, uint16_t* d_out, void* stream);
 int fac_debug_conv(fac_ctx* ctx, int layer, const uint16_t* d_in, int B, uint16_t* d_out, void* stream);
@@ -143,6 +161,16 @@ int fac_debug_tail(fac_ctx* ctx, const uint16_t* d_stem, int B, const int32_t* d
                    void* stream);
 int fac_debug_gemm(fac_ctx* ctx, int epi, const uint16_t* d_a, const uint16_t* d_w, const float* d_bias, void* d_out,
                    int M, int N, int K, int splits, int variant, void* stream);
+int fac_debug_embed_ln(fac_ctx* ctx, const float* d_slab, int S, int B, const float* d_bias, const float* d_cls,
+                       const float* d_pos, const int32_t* d_pos_index, float* d_x, const float* d_g, const float* d_b,
+                       uint16_t* d_y, void* stream);
+int fac_debug_resid_ln(fac_ctx* ctx, float* d_x, const float* d_slab, int S, const float* d_bias, const float* d_g,
+                       const float* d_b, uint16_t* d_y, int R, float eps, void* stream);
+int fac_debug_resid_cls(fac_ctx* ctx, const float* d_x, const float* d_slab, int S, const float* d_bias,
+                        uint16_t* d_c, int B, void* stream);
+int fac_debug_attention(fac_ctx* ctx, const float* d_qkv, uint16_t* d_o, int B, float scale, void* stream);
+int fac_debug_head_out(fac_ctx* ctx, const float* d_hid, const float* d_w2, const float* d_b2, float* d_logits,
+                       float* d_probs, int B, void* stream);
 int fac_profile_forward_u8(fac_ctx* ctx, const uint8_t* d_in, int B, const int32_t* d_pos_index, float* d_logits,
                            float* stage_ms, int n_stages, void* stream);
 

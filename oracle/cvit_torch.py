@@ -196,16 +196,29 @@ def conv_block_emulated(sd, h: torch.Tensor, i: int, dtype: str = "bf16") -> tor
 
 
 @torch.no_grad()
-def tail_emulated(sd, h: torch.Tensor, pos_index=None, dtype: str = "bf16"):
-    """Stem output (16-bit valued) -> logits with the HIP path's rounding points."""
+def tail_emulated(sd, h: torch.Tensor, pos_index=None, dtype: str = "bf16", ff_eps: float = LN_EPS,
+                  proj_splits: int = 1):
+    """Stem output (16-bit valued) -> logits with the HIP path's rounding points.
+    ff_eps: eps of the FeedForward PreNorm LayerNorm (the context option
+    "ffn_ln_eps_exp").  proj_splits: the two N = 1024 projections (to_out, FF2)
+    summed as that many K ranges in fp32, in split order (option "proj_splits")."""
     sd = to_torch_sd(sd)
     r = lambda t: round_to(t, dtype)  # noqa: E731
     B = h.shape[0]
     y = h.permute(0, 2, 3, 1).reshape(B, 1, -1)
     y = F.linear(y, r(sd["patch_to_embedding.weight"]), sd["patch_to_embedding.bias"])
     x = torch.cat((sd["cls_token"].expand(B, -1, -1), y), 1) + _pos_rows(sd, pos_index, B)
-    lin = lambda inp, w, b=None: F.linear(inp, r(w), b)  # noqa: E731
-    x = _transformer(sd, x, lin=lin, act_round=r)
+
+    def lin(inp, w, b=None):
+        if proj_splits == 1 or w.shape[0] != 1024:
+            return F.linear(inp, r(w), b)
+        kp = w.shape[1] // proj_splits
+        parts = [F.linear(inp[..., s * kp:(s + 1) * kp], r(w[:, s * kp:(s + 1) * kp])) for s in range(proj_splits)]
+        acc = parts[0]
+        for part in parts[1:]:
+            acc = acc + part
+        return acc + b
+    x = _transformer(sd, x, lin=lin, act_round=r, ff_eps=ff_eps)
     c = r(x[:, 0])
     hh = F.relu(F.linear(c, r(sd["mlp_head.0.weight"]), sd["mlp_head.0.bias"]))
     return F.linear(hh, sd["mlp_head.2.weight"], sd["mlp_head.2.bias"])
