@@ -54,6 +54,17 @@ hipError_t launch_clip_stage(const uint8_t* frames, int n_frames, int H, int W, 
 hipError_t launch_stem224(int dtype, bool u8, const void* in, const uint16_t* w1, const float* b1, const uint16_t* w2,
                           const float* b2, const uint16_t* w3, const float* b3, uint16_t* out, int B, int nwg,
                           hipStream_t s);
+// gradcam.hip: the tail's input-gradient kernels
+size_t dgrad_partial_floats(int M, int N, int K);
+hipError_t launch_dgrad(int dtype, const float* dY, int ldy, const uint16_t* W, float* P, int M, int N, int K,
+                        int* splits, hipStream_t st);
+hipError_t launch_dgrad_reduce(int mode, const float* P, int S, size_t MK, const float* pre, float* out,
+                               hipStream_t st);
+hipError_t launch_ln_bwd(const float* x, const float* g, float eps, const float* P, int S, int R, float* dx,
+                         hipStream_t st);
+hipError_t launch_attn2_bwd(const float* qkv, const float* P, int S, int B, float scale, float* dqkv, hipStream_t st);
+hipError_t launch_head_bwd(const float* hid, const float* w2, const int32_t* target, const float* logits, int B,
+                           float* dhid, hipStream_t st);
 enum { EPI_F32 = 0, EPI_F32_RELU = 1, EPI_T_GELU = 2, EPI_RESID = 3, EPI_PARTIAL = 4, EPI_T = 5 };
 }  // namespace fac
 
@@ -209,6 +220,19 @@ struct fac_ctx {
   int32_t* g_pidx = nullptr;
   float* g_out = nullptr;  // logits [graph_max_b][2], then probs [graph_max_b][2]
   int g_cap = 0;           // crops the g_* buffers hold
+  // Grad-CAM (fac_gradcam_tail): what the recording tail forward keeps for the
+  // backward, and the backward's own buffers; one allocation, made on the
+  // first call and regrown only for a larger B.  With R = 2B rows:
+  //   rec_x    [12][R][1024]  the residual stream each LayerNorm read (2 per layer)
+  //   rec_qkv  [6][R][3072]   q, k, v (the softmax is recomputed from them)
+  //   rec_pre  [6][R][2048]   FF1 before the GELU
+  //   (the head's hidden vector is the context's hh, untouched until the next forward)
+  //   gc_dx [R][1024], gc_t [R][3072] (dpre / dqkv / dhid), gc_p: the dgrad partials
+  //   gc_ain [B][14][14][512] 16-bit: the last conv's input (fac_gradcam_features)
+  void* gc_ws = nullptr;
+  int gc_cap = 0;
+  float *rec_x = nullptr, *rec_qkv = nullptr, *rec_pre = nullptr, *gc_dx = nullptr, *gc_t = nullptr, *gc_p = nullptr;
+  uint16_t* gc_ain = nullptr;
 };
 
 namespace {
@@ -547,7 +571,8 @@ struct Prof {
 };
 
 int tail_impl(fac_ctx* c, const uint16_t* stem, int B, const int32_t* pidx, float* logits, float* probs,
-              hipStream_t st, Prof* prof, float* hidden_out = nullptr, bool beside_stack = false);
+              hipStream_t st, Prof* prof, float* hidden_out = nullptr, bool beside_stack = false,
+              bool rec = false);
 
 // The synchronous forward on `stream`: conv stack -> stem_dst (default the
 // context's stem buffer 0), then (unless conv_only) the encoder and head.
@@ -696,8 +721,13 @@ int forward_impl(fac_ctx* c, const void* in, bool u8, int B, const int32_t* pidx
 
 // Patch embedding, the 6 encoder layers and the head on `st`, from the conv
 // stack's output `stem` [B,7,7,512] (cvit.py:171-179).
+// rec (fac_gradcam_tail): the same launches, keeping what the backward reads
+// (fac_ctx::rec_*): the residual stream is copied out after each kernel that
+// finishes a LayerNorm's input, the QKV GEMM writes straight into the record
+// (attention2 reads it there), and FF1 runs once more with the plain fp32
+// epilogue for its pre-activation.  No kernel that feeds the logits changes.
 int tail_impl(fac_ctx* c, const uint16_t* stem, int B, const int32_t* pidx, float* logits, float* probs,
-              hipStream_t st, Prof* prof, float* hidden_out, bool beside_stack) {
+              hipStream_t st, Prof* prof, float* hidden_out, bool beside_stack, bool rec) {
   using namespace fac;
   const int dt = c->dtype;
   // beside_stack: this encoder co-runs with the next batch's conv stack (the
@@ -722,6 +752,14 @@ int tail_impl(fac_ctx* c, const uint16_t* stem, int B, const int32_t* pidx, floa
                                       c->tl[0].ln1_b, c->xn, c->errflag, ++c->fwd_seq, st));
   MARK(17);
   const int R = 2 * B;
+  const size_t xrow = (size_t)R * kDim;
+  int nrec = 0;  // LayerNorm inputs recorded so far
+#define REC_X()                                                                                          \
+  do {                                                                                                   \
+    if (rec)                                                                                             \
+      HIP_TRY(c, hipMemcpyAsync(c->rec_x + (size_t)(nrec++) * xrow, c->x, xrow * 4, hipMemcpyDeviceToDevice, st)); \
+  } while (0)
+  REC_X();
   const float scale = 1.0f / std::sqrt((float)kDim);  // dim ** -0.5 (cvit.py:38), not head_dim
   // The two N=1024 projections (to_out, FF2) run split-K into fp32 partial
   // slabs; the following kernel (residual add + next LayerNorm, or the CLS
@@ -731,13 +769,19 @@ int tail_impl(fac_ctx* c, const uint16_t* stem, int B, const int32_t* pidx, floa
     const TLayer& T = c->tl[l];
     if (l > 0) {
       HIP_TRY(c, launch_resid_layernorm(dt, c->x, c->slab, SK, c->tl[l - 1].b2, T.ln1_g, T.ln1_b, c->xn, R, st));
+      REC_X();
     }
-    HIP_TRY(c, launch_gemm(dt, EPI_F32, c->xn, kDim, T.wqkv, kDim, nullptr, c->qkv, 3 * kDim, R, 3 * kDim, kDim, 1, st,
+    float* qkv = rec ? c->rec_qkv + (size_t)l * R * 3 * kDim : c->qkv;
+    HIP_TRY(c, launch_gemm(dt, EPI_F32, c->xn, kDim, T.wqkv, kDim, nullptr, qkv, 3 * kDim, R, 3 * kDim, kDim, 1, st,
                            gv[1]));
-    HIP_TRY(c, launch_attention2(dt, c->qkv, c->o, B, scale, st));
+    HIP_TRY(c, launch_attention2(dt, qkv, c->o, B, scale, st));
     HIP_TRY(c, launch_gemm(dt, EPI_PARTIAL, c->o, kDim, T.wo, kDim, nullptr, c->slab, kDim, R, kDim, kDim, SK, st,
                            gv[2]));
     HIP_TRY(c, launch_resid_layernorm(dt, c->x, c->slab, SK, T.bo, T.ln2_g, T.ln2_b, c->xn, R, st, c->ffn_ln_eps));
+    REC_X();
+    if (rec)
+      HIP_TRY(c, launch_gemm(dt, EPI_F32, c->xn, kDim, T.w1, kDim, T.b1, c->rec_pre + (size_t)l * R * kMlp, kMlp, R, kMlp,
+                             kDim, 1, st, gv[3]));
     HIP_TRY(c, launch_gemm(dt, EPI_T_GELU, c->xn, kDim, T.w1, kDim, T.b1, c->hbuf, kMlp, R, kMlp, kDim, 1, st,
                            gv[3]));
     HIP_TRY(c, launch_gemm(dt, EPI_PARTIAL, c->hbuf, kMlp, T.w2, kMlp, nullptr, c->slab, kDim, R, kDim, kMlp, SK, st, gv[4]));
@@ -751,6 +795,76 @@ int tail_impl(fac_ctx* c, const uint16_t* stem, int B, const int32_t* pidx, floa
   if (logits) HIP_TRY(c, launch_head_out(hh, c->h2_w, c->h2_b, logits, probs, B, st));
   MARK(19);
 #undef MARK
+#undef REC_X
+  return FAC_OK;
+}
+
+// The Grad-CAM buffers of fac_ctx for B crops (see fac_ctx::gc_ws).
+int ensure_gc(fac_ctx* c, int B) {
+  if (B <= c->gc_cap && c->gc_ws) return FAC_OK;
+  auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  const size_t R = 2 * (size_t)B;
+  size_t pmax = 0;  // the largest dgrad's partials
+  const int shp[6][3] = {{B, kMlp, kDim},      {(int)R, kDim, kMlp},     {(int)R, kMlp, kDim},
+                         {(int)R, kDim, kDim}, {(int)R, 3 * kDim, kDim}, {B, kDim, kPatchDim}};
+  for (auto& s : shp) pmax = std::max(pmax, fac::dgrad_partial_floats(s[0], s[1], s[2]));
+  const size_t n_x = al(12 * R * kDim * 4), n_q = al(6 * R * 3 * kDim * 4), n_p = al(6 * R * kMlp * 4),
+               n_dx = al(R * kDim * 4), n_t = al(R * 3 * kDim * 4), n_pp = al(pmax * 4),
+               n_a = al((size_t)B * 14 * 14 * 512 * 2);
+  if (c->gc_ws) {
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipFree(c->gc_ws));
+    c->gc_ws = nullptr;
+    c->gc_cap = 0;
+  }
+  const size_t total = n_x + n_q + n_p + n_dx + n_t + n_pp + n_a;
+  if (hipMalloc(&c->gc_ws, total) != hipSuccess) {
+    c->gc_ws = nullptr;
+    return set_err(c, FAC_ERR_OOM, "Grad-CAM workspace allocation of " + std::to_string(total) + " bytes failed");
+  }
+  char* p = (char*)c->gc_ws;
+  c->rec_x = (float*)p; p += n_x;
+  c->rec_qkv = (float*)p; p += n_q;
+  c->rec_pre = (float*)p; p += n_p;
+  c->gc_dx = (float*)p; p += n_dx;
+  c->gc_t = (float*)p; p += n_t;
+  c->gc_p = (float*)p; p += n_pp;
+  c->gc_ain = (uint16_t*)p;
+  c->gc_cap = B;
+  return FAC_OK;
+}
+
+// d logits[b][target[b]] / d stem after a recording tail forward (everything
+// tail_impl(rec) kept is still in place): cvit.py:167-179 in reverse, fp32.
+// Each dgrad GEMM leaves split partials in gc_p and the kernel after it adds
+// them in split order while doing its own step.
+int tail_backward(fac_ctx* c, int B, const int32_t* target, const float* logits, float* grad_feat, hipStream_t st) {
+  using namespace fac;
+  const int dt = c->dtype, R = 2 * B;
+  const float scale = 1.0f / std::sqrt((float)kDim);
+  int S = 0;
+  // head: one-hot seed -> hidden (ReLU mask) -> the CLS rows of the residual gradient
+  HIP_TRY(c, launch_head_bwd(c->hh, c->h2_w, target, logits, B, c->gc_t, st));
+  HIP_TRY(c, launch_dgrad(dt, c->gc_t, kMlp, c->h1_w, c->gc_p, B, kMlp, kDim, &S, st));
+  HIP_TRY(c, launch_dgrad_reduce(2, c->gc_p, S, (size_t)B * kDim, nullptr, c->gc_dx, st));
+  for (int l = kDepth - 1; l >= 0; --l) {
+    const TLayer& T = c->tl[l];
+    const float* xa = c->rec_x + (size_t)(2 * l) * R * kDim;  // LN1's input; LN2's follows it
+    const float* xb = xa + (size_t)R * kDim;
+    // FeedForward: FF2 dgrad, GELU', FF1 dgrad, LayerNorm backward into dx
+    HIP_TRY(c, launch_dgrad(dt, c->gc_dx, kDim, T.w2, c->gc_p, R, kDim, kMlp, &S, st));
+    HIP_TRY(c, launch_dgrad_reduce(1, c->gc_p, S, (size_t)R * kMlp, c->rec_pre + (size_t)l * R * kMlp, c->gc_t, st));
+    HIP_TRY(c, launch_dgrad(dt, c->gc_t, kMlp, T.w1, c->gc_p, R, kMlp, kDim, &S, st));
+    HIP_TRY(c, launch_ln_bwd(xb, T.ln2_g, c->ffn_ln_eps, c->gc_p, S, R, c->gc_dx, st));
+    // Attention: to_out dgrad, the 2-token attention backward, QKV dgrad, LayerNorm backward
+    HIP_TRY(c, launch_dgrad(dt, c->gc_dx, kDim, T.wo, c->gc_p, R, kDim, kDim, &S, st));
+    HIP_TRY(c, launch_attn2_bwd(c->rec_qkv + (size_t)l * R * 3 * kDim, c->gc_p, S, B, scale, c->gc_t, st));
+    HIP_TRY(c, launch_dgrad(dt, c->gc_t, 3 * kDim, T.wqkv, c->gc_p, R, 3 * kDim, kDim, &S, st));
+    HIP_TRY(c, launch_ln_bwd(xa, T.ln1_g, 1e-5f, c->gc_p, S, R, c->gc_dx, st));
+  }
+  // cls and pos are additive: only the patch token's row (2b+1) goes on through the patch embedding
+  HIP_TRY(c, launch_dgrad(dt, c->gc_dx + kDim, 2 * kDim, c->pe_w, c->gc_p, B, kDim, kPatchDim, &S, st));
+  HIP_TRY(c, launch_dgrad_reduce(0, c->gc_p, S, (size_t)B * kPatchDim, nullptr, grad_feat, st));
   return FAC_OK;
 }
 
@@ -1183,6 +1297,57 @@ int fac_pipeline_join(fac_ctx* c, int keep, void* stream) {
   return FAC_OK;
 }
 
+int fac_gradcam_tail(fac_ctx* c, const void* d_feat, int B, const int32_t* d_pos, const int32_t* d_target,
+                     float* d_logits, float* d_grad_feat, void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!c->loaded) return set_err(c, FAC_ERR_NOT_LOADED, "fac_gradcam_tail before fac_load_weights");
+  if (!d_feat || !d_pos || !d_target || !d_logits || !d_grad_feat || B <= 0)
+    return set_err(c, FAC_ERR_ARG, "bad fac_gradcam_tail arguments");
+  if (B > 32) return set_err(c, FAC_ERR_SHAPE, "fac_gradcam_tail takes at most 32 crops (one per pos_embedding slot)");
+  if (int e = take_device_error(c)) return e;
+  DevGuard g(c->device);
+  int rc = ensure_ws(c, B);
+  if (rc) return rc;
+  rc = ensure_gc(c, B);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(c, hipStreamIsCapturing(st, &cs));
+  if (cs == hipStreamCaptureStatusNone) {
+    rc = order_on(c, st);  // the shared encoder buffers: after the context's previous forward on any stream
+    if (rc) return rc;
+  }
+  rc = tail_impl(c, (const uint16_t*)d_feat, B, d_pos, d_logits, nullptr, st, nullptr, nullptr, false, true);
+  if (rc) return rc;
+  rc = tail_backward(c, B, d_target, d_logits, d_grad_feat, st);
+  if (rc) return rc;
+  return cs == hipStreamCaptureStatusNone ? mark_done(c, st) : FAC_OK;
+}
+
+int fac_gradcam_features(fac_ctx* c, const void* d_in, int u8, int B, uint16_t* d_map, uint16_t* d_feat,
+                         void* stream) {
+  if (!c) return FAC_ERR_ARG;
+  if (!c->loaded) return set_err(c, FAC_ERR_NOT_LOADED, "fac_gradcam_features before fac_load_weights");
+  if (c->tail_only) return set_err(c, FAC_ERR_NOT_LOADED, "tail-only context has no conv stem");
+  if (!d_in || !d_map || !d_feat || B <= 0) return set_err(c, FAC_ERR_ARG, "bad fac_gradcam_features arguments");
+  if (B > 32) return set_err(c, FAC_ERR_SHAPE, "fac_gradcam_features takes at most 32 crops");
+  DevGuard g(c->device);
+  int rc = ensure_gc(c, B);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // conv1..conv16 as the forward runs them; conv16's output is conv17's input
+  rc = forward_impl(c, d_in, u8 != 0, B, nullptr, nullptr, nullptr, stream, nullptr, 15, c->gc_ain);
+  if (rc) return rc;
+  const ConvLayer& L = c->conv[15];
+  // conv17 + folded BN alone: the pre-ReLU, pre-pool map; then the forward's own fused launch
+  HIP_TRY(c, fac::launch_conv3x3(c->dtype, c->gc_ain, L.w, L.b, d_map, B, L.H, L.H, L.Cin, L.Cout, false, c->zero16, st,
+                                 false));
+  HIP_TRY(c, run_conv(c, L, c->gc_ain, d_feat, B, st));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(c, hipStreamIsCapturing(st, &cs));
+  return cs == hipStreamCaptureStatusNone ? mark_done(c, st) : FAC_OK;
+}
+
 int fac_debug_gemm(fac_ctx* c, int epi, const uint16_t* d_a, const uint16_t* d_w, const float* d_bias, void* d_out,
                    int M, int N, int K, int splits, int variant, void* stream) {
   if (!c || !d_a || !d_w || !d_out) return set_err(c, FAC_ERR_ARG, "bad debug_gemm arguments");
@@ -1357,6 +1522,7 @@ void fac_destroy(fac_ctx* c) {
     if (c->g_out) (void)hipFree(c->g_out);
     for (void* p : c->weights) (void)hipFree(p);
     if (c->ws) (void)hipFree(c->ws);
+    if (c->gc_ws) (void)hipFree(c->gc_ws);
     if (c->err_host) (void)hipHostFree(c->err_host);
   }
   delete c;

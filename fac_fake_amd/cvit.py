@@ -357,6 +357,36 @@ class CViT(nn.Module):
         _lib.check(lib.fac_pipeline_join(self._ctx, 0, stream), self._ctx, "fac_pipeline_join")
         return logits
 
+    # ------------------------------------------------------------------ Grad-CAM (fac_fake_amd/gradcam.py)
+    def gradcam_features(self, x: torch.Tensor, u8: bool):
+        """(A, feat): the last BatchNorm's output before ReLU and MaxPool (features[-3], 16-bit NHWC
+        [B,14,14,512]) and the stem output the forward computes ([B,7,7,512], bit-identical to it)."""
+        with self._lock:
+            lib = self._ensure_ctx(x.device)
+            B = x.shape[0]
+            t16 = torch.float16 if self.dtype_name == "fp16" else torch.bfloat16
+            a = torch.empty(B, 14, 14, 512, dtype=t16, device=x.device)
+            feat = torch.empty(B, 7, 7, 512, dtype=t16, device=x.device)
+            _lib.check(lib.fac_gradcam_features(self._ctx, x.data_ptr(), int(u8), B, a.data_ptr(), feat.data_ptr(),
+                                                torch.cuda.current_stream(x.device).cuda_stream), self._ctx,
+                       "fac_gradcam_features")
+            return a, feat
+
+    def gradcam_tail(self, feat: torch.Tensor, pos_index, target: torch.Tensor):
+        """(logits [B,2], d logits[b][target[b]] / d feat as fp32 [B,7,7,512]); target int32 [B] on the
+        device, -1 = the crop's argmax.  The logits are bit-identical to the forward's."""
+        with self._lock:
+            lib = self._ensure_ctx(feat.device)
+            B = feat.shape[0]
+            pidx = self._pos_index(B, pos_index, feat.device)
+            logits = torch.empty(B, 2, dtype=torch.float32, device=feat.device)
+            grad = torch.empty(B, 7, 7, 512, dtype=torch.float32, device=feat.device)
+            _lib.check(lib.fac_gradcam_tail(self._ctx, feat.data_ptr(), B, pidx.data_ptr(), target.data_ptr(),
+                                            logits.data_ptr(), grad.data_ptr(),
+                                            torch.cuda.current_stream(feat.device).cuda_stream), self._ctx,
+                       "fac_gradcam_tail")
+            return logits, grad
+
     def forward_u8(self, crops: torch.Tensor, pos_index=None, return_probs: bool = False):
         """uint8 NHWC RGB face crops [B,224,224,3] -> logits (and per-logit sigmoids)."""
         if crops.dtype != torch.uint8 or crops.dim() != 4 or tuple(crops.shape[1:]) != (224, 224, 3):

@@ -246,9 +246,10 @@ class CViT(nn.Module):
         _lib.check(_lib.load().fac_reserve(self._ctx, int(max_batch)), self._ctx, "fac_reserve")
 
     # ------------------------------------------------------------------ forward
-    def features(self, src: torch.Tensor, u8: bool) -> torch.Tensor:
+    def features(self, src: torch.Tensor, u8: bool, layers=None) -> torch.Tensor:
         """features1 + features2 (:432-435) -> [B,7,7,512] 16-bit NHWC.  src:
-        uint8 NHWC crops (u8) or normalised fp32 NCHW images."""
+        uint8 NHWC crops (u8) or normalised fp32 NCHW images.  layers: the convs
+        after the fused first block to run (default all of them)."""
         lib = _lib.load()
         dti = _lib.DTYPES[self.dtype_name]
         B, dev = src.shape[0], src.device
@@ -258,13 +259,51 @@ class CViT(nn.Module):
         _lib.check(lib.fac_stem224(dti, int(u8), src.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
                                    b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), x.data_ptr(), B, st), None,
                    "fac_stem224")
-        for wpk, b, H, ci, co, pl, relu in self._layers:
+        for wpk, b, H, ci, co, pl, relu in (self._layers if layers is None else layers):
             Ho = H // 2 if pl else H
             y = torch.empty(B, Ho, Ho, co, dtype=x.dtype, device=dev)
             _lib.check(lib.fac_conv3x3(dti, x.data_ptr(), wpk.data_ptr(), b.data_ptr(), y.data_ptr(), B, H, ci, co,
                                        int(pl), int(relu), self._zero.data_ptr(), st), None, "fac_conv3x3")
             x = y
         return x
+
+    # ------------------------------------------------------------------ Grad-CAM (fac_fake_amd/gradcam.py)
+    def gradcam_features(self, src: torch.Tensor, u8: bool):
+        """(A, feat): features2[-3]'s output, the last BatchNorm before ReLU and MaxPool (16-bit NHWC
+        [B,14,14,512]), and features2's output as features() gives it ([B,7,7,512], bit-identical): the
+        last conv runs twice on the same input, once with relu = pool = 0."""
+        self._prepare(src.device)
+        lib = _lib.load()
+        dti = _lib.DTYPES[self.dtype_name]
+        x = self.features(src, u8, self._layers[:-1])
+        wpk, b, H, ci, co, _pl, _relu = self._layers[-1]
+        B, st = x.shape[0], torch.cuda.current_stream(x.device).cuda_stream
+        a = torch.empty(B, H, H, co, dtype=x.dtype, device=x.device)
+        feat = torch.empty(B, H // 2, H // 2, co, dtype=x.dtype, device=x.device)
+        for out, pl, relu in ((a, 0, 0), (feat, 1, 1)):
+            _lib.check(lib.fac_conv3x3(dti, x.data_ptr(), wpk.data_ptr(), b.data_ptr(), out.data_ptr(), B, H, ci, co,
+                                       pl, relu, self._zero.data_ptr(), st), None, "fac_conv3x3")
+        return a, feat
+
+    def gradcam_tail(self, feat: torch.Tensor, pos_index, target: torch.Tensor):
+        """(logits [B,2], d logits[b][target[b]] / d feat as fp32 [B,7,7,512]) through x * GGCA(x) and the
+        tail; target int32 [B] on the device, -1 = the crop's argmax."""
+        self._prepare(feat.device)
+        lib = _lib.load()
+        B, dev = feat.shape[0], feat.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        pidx = _pos_index(B, pos_index, dev)
+        wf = self.weighted_features16(feat)
+        logits = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        gw = torch.empty(B, 7, 7, 512, dtype=torch.float32, device=dev)
+        _lib.check(lib.fac_gradcam_tail(self._ctx, wf.data_ptr(), B, pidx.data_ptr(), target.data_ptr(),
+                                        logits.data_ptr(), gw.data_ptr(), st), self._ctx, "fac_gradcam_tail")
+        grad = torch.empty_like(gw)
+        w1, b1, bn4, w2, b2 = self._ggca
+        _lib.check(lib.fac_ggca_mul_bwd(_lib.DTYPES[self.dtype_name], feat.data_ptr(), gw.data_ptr(), B, 7, 7, 512, 4,
+                                        w1.data_ptr(), b1.data_ptr(), bn4.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                        grad.data_ptr(), st), None, "fac_ggca_mul_bwd")
+        return logits, grad
 
     def weighted_features16(self, f: torch.Tensor) -> torch.Tensor:
         """x * GGCA(x) (:436-437) on [B,(1,)7,7,512] 16-bit NHWC."""

@@ -232,6 +232,80 @@ int fac_crop_resize_u8(const uint8_t* d_frames, int n_frames, int H, int W, cons
 int fac_clip_stage_u8(const uint8_t* d_frames, int n_frames, int H, int W, const int32_t* d_boxes, int n_boxes, int T,
                       uint8_t* d_clips, void* stream);
 
+/* Grad-CAM (CViT-main/figure/gradcam_cnn.py, figure/utils.py:57-166) ---------
+ * The heatmap of one logit over the last BatchNorm's 512 x 14 x 14 map A
+ * (features[-3] / features2[-3], before ReLU and MaxPool).  The library is
+ * forward-only except for these entry points, which compute input gradients
+ * (never weight gradients) in fp32, with the forward's 16-bit roundings taken
+ * as identity.  Every sum has one fixed order and no atomics: a crop's
+ * gradient and heatmap are bit-reproducible and do not depend on the batch
+ * (only on its pos slot).  B <= 32.  fac_fake_amd/gradcam.py drives them.
+ *
+ * fac_gradcam_features: conv1..conv16 as the forward runs them, then conv17 +
+ * folded BN twice: once alone into d_map (16-bit NHWC [B,14,14,512], A) and
+ * once as the forward's fused conv + ReLU + pool into d_feat ([B,7,7,512], bit-
+ * identical to the forward's stem output).  d_in: uint8 NHWC crops (u8 != 0)
+ * or normalised fp32 NCHW images.
+ *
+ * fac_gradcam_tail: fac_forward_features' launches on d_feat (the logits are
+ * bit-identical to it), keeping the residual stream before each of the 12
+ * LayerNorms, q/k/v, the FF1 pre-activations and the head's hidden vector in
+ * a context-owned workspace (allocated on the first call, regrown only for a
+ * larger B; about 1.4 MB per crop), then the backward: d_grad_feat (fp32
+ * [B,7,7,512]) = d logits[b][t_b] / d d_feat, t_b = d_target[b] (int32 [B]; a
+ * negative entry means the argmax of the crop's logits).  Honours
+ * "ffn_ln_eps_exp" like the forward. */
+int fac_gradcam_features(fac_ctx* ctx, const void* d_in, int u8, int B, uint16_t* d_map, uint16_t* d_feat,
+                         void* stream);
+int fac_gradcam_tail(fac_ctx* ctx, const void* d_feat, int B, const int32_t* d_pos_index, const int32_t* d_target,
+                     float* d_logits, float* d_grad_feat, void* stream);
+
+/* The backward's kernels on their own (all device pointers; fp32 unless said).
+ * fac_gradcam_dgrad: dX[M][K] = dY[M][N] . W[N][K], W the 16-bit weight as the
+ * forward GEMMs store it (rows of N; no transposed copy), dY rows ldy floats
+ * apart, M <= 64, K % 4 == 0 (FAC_ERR_SHAPE otherwise, or for a W not 8-byte /
+ * a scratch not 16-byte aligned).  W is streamed once per 8 rows of dY by
+ * workgroups that each own 1024 columns and one range of W's rows; their
+ * partial sums go to d_scratch (fac_gradcam_dgrad_scratch_floats(M, N, K)
+ * floats) and are added in range order.
+ * fac_gradcam_gelu_bwd: dpre = dh * GELU'(pre), exact-erf GELU, n elements.
+ * fac_gradcam_ln_bwd: dx[r] += LayerNorm-backward(dy[r]; x[r], g, eps), R rows
+ * of 1024 (input gradient only).
+ * fac_gradcam_attention_bwd: the backward of fac_debug_attention (2 tokens, 8
+ * heads x 128): qkv and dqkv [2B][3072], do [2B][1024]; the softmax is
+ * recomputed from q and k.
+ * fac_gradcam_head_bwd: dhid[b][j] = w2[t_b][j] where hid[b][j] > 0, else 0
+ * (hid [B][2048] after ReLU, w2 [2][2048], t_b as for fac_gradcam_tail).
+ * fac_ggca_mul_bwd: the backward of fac_ggca (out = x * x * att_h * att_w):
+ * x 16-bit [n][h][w][c], g = d out and dx fp32 of that shape; weights as
+ * fac_ggca takes them.  Max pools send their gradient to the first maximum
+ * (AdaptiveMaxPool2d's scan).  FAC_ERR_SHAPE unless c/groups is a multiple
+ * of 16, h*w*c/groups <= 6272 and (2h + 2w)*c/groups <= 3584 (held in LDS).
+ * fac_relu_pool_bwd: a 16-bit [n][2h][2h][c] before ReLU + MaxPool2d(2,2),
+ * dp [n][h][h][c]; da [n][2h][2h][c] = dp at the window's first maximum
+ * (row-major) where a > 0, else 0.
+ * fac_gradcam_cam: utils.py:76-134,165-166 for a 16-bit [n][14][14][512] and
+ * da fp32 of that shape: w = mean_p da (to d_w [n][512] unless null), cam =
+ * max(sum_c w a, 0), min/max scaled -> d_cam14 [n][14][14]; resized bilinearly
+ * (half-pixel centres, clamped) to 224 x 224, max(., 0), scaled again ->
+ * d_heat [n][224][224].  A crop whose cam is all <= 0 gives exact zeros. */
+size_t fac_gradcam_dgrad_scratch_floats(int M, int N, int K);
+int fac_gradcam_dgrad(int dtype, const float* d_dy, int ldy, const uint16_t* d_w, float* d_scratch, float* d_dx,
+                      int M, int N, int K, void* stream);
+int fac_gradcam_gelu_bwd(const float* d_pre, const float* d_dh, long long n, float* d_dpre, void* stream);
+int fac_gradcam_ln_bwd(const float* d_x, const float* d_g, float eps, const float* d_dy, int R, float* d_dx,
+                       void* stream);
+int fac_gradcam_attention_bwd(const float* d_qkv, const float* d_do, int B, float scale, float* d_dqkv,
+                              void* stream);
+int fac_gradcam_head_bwd(const float* d_hid, const float* d_w2, const int32_t* d_target, const float* d_logits,
+                         int B, float* d_dhid, void* stream);
+int fac_ggca_mul_bwd(int dtype, const void* x, const float* g, int n, int h, int w, int c, int groups,
+                     const float* w1, const float* b1, const float* bn4, const float* w2, const float* b2, float* dx,
+                     void* stream);
+int fac_relu_pool_bwd(int dtype, const void* a, const float* dp, int n, int h, int c, float* da, void* stream);
+int fac_gradcam_cam(int dtype, const void* a, const float* da, int n, float* d_w, float* d_cam14, float* d_heat,
+                    void* stream);
+
 /* Tuning knob: run the conv stem in sub-batches of `crops` crops (0 = whole
  * batch), so intermediate activations stay resident in the Infinity Cache. */
 int fac_set_stem_chunk(fac_ctx* ctx, int crops);
