@@ -57,21 +57,47 @@ detector = None                 # set by load_detector(): scores videos that car
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
 
-def load_model(weights: str | None = None, dtype: str = "fp16", dev: str | None = None):
+MODEL_NAMES = ("cvit", "cvit_GGCA_ADD_DEConv_RepBn8", "cvit_DEConv", "cvit_GGCA_ADD", "cvit_GGCA_ADD_DEConv",
+               "cvit_GGCA_ADD_RepBn", "cvit_GGCA_ADD_DEConv_RepBn", "cvit_GGCA_ADD_DEConv_RepBn3",
+               "cvit_GGCA_ADD_DEConv_RepBn4", "cvit_GGCA_ADD_DEConv_RepBn5")   # the reference's model/<name>.py
+
+
+def model_class(name: str | None = None):
+    """The drop-in ``CViT`` class of ``model/<name>.py``; None is the base ``cvit``."""
+    if name in (None, "cvit"):
+        from fac_fake_amd.cvit import CViT
+        return CViT
+    if name == "cvit_GGCA_ADD_DEConv_RepBn8":
+        from fac_fake_amd.repbn8 import CViT
+        return CViT
+    from fac_fake_amd.variants import variant_class
+    return variant_class(name)
+
+
+def _synthetic_state_dict(name: str | None):
+    from fac_fake_amd import weights as W
+    if name in (None, "cvit"):
+        return W.make_state_dict(0)
+    if name == "cvit_GGCA_ADD_DEConv_RepBn8":
+        return W.make_repbn8_state_dict(0)
+    return W.make_variant_state_dict(name, 0)
+
+
+def load_model(weights: str | None = None, dtype: str = "fp16", dev: str | None = None, name: str | None = None):
     """``CViT(224, 7, 2, 512, 1024, 6, 8, 2048)`` + ``load_state_dict`` + ``eval``
     (cvit_prediction.py:62-70).  ``weights``: a state_dict checkpoint as
     ``cvit_train.py:210`` saves it (loaded with ``weights_only=True``), or
     None for the deterministic synthetic weights (the reference ships no
-    trained checkpoint)."""
+    trained checkpoint).  ``name``: which ``model/<name>.py`` class the
+    checkpoint belongs to (the reference edits its `from cvit import CViT` line, :23);
+    None is the base ``cvit``."""
     global model
-    from fac_fake_amd.cvit import CViT
-    from fac_fake_amd.weights import make_state_dict
-    m = CViT(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8, mlp_dim=2048,
-             dtype=dtype)
+    m = model_class(name)(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
+                          mlp_dim=2048, dtype=dtype)
     if weights:
         sd = torch.load(weights, map_location="cpu", weights_only=True)
     else:
-        sd = {k: torch.from_numpy(np.asarray(v)) for k, v in make_state_dict(0).items()}
+        sd = {k: torch.from_numpy(np.asarray(v)) for k, v in _synthetic_state_dict(name).items()}
     m.load_state_dict(sd)
     m.to(dev or device)
     m.eval()
@@ -242,6 +268,8 @@ def main(argv=None):
     ap.add_argument("--csv", default=save_csv_path)
     ap.add_argument("--weights", default=None, help="CViT state_dict checkpoint (default: synthetic weights)")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
+    ap.add_argument("--model", default="cvit", choices=MODEL_NAMES,
+                    help="the reference's model/<name>.py class the weights belong to (default: the base cvit)")
     ap.add_argument("--metadata", default=None, help="json {filename: 0/1} for the accuracy")
     ap.add_argument("--num-workers", type=int, default=1)
     ap.add_argument("--detect", action="store_true",
@@ -250,7 +278,7 @@ def main(argv=None):
     ap.add_argument("--detector-anchors", default=None, help="anchors.npy (with --detector-weights)")
     args = ap.parse_args(argv)
     sample, save_csv_path = args.sample, args.csv
-    load_model(args.weights, args.dtype)
+    load_model(args.weights, args.dtype, name=args.model)
     if args.detect:
         load_detector(args.detector_weights, args.detector_anchors)
     filenames = sorted(x for x in os.listdir(sample) if x.endswith(".npz"))
@@ -264,7 +292,7 @@ def main(argv=None):
     return predictions
 
 
-__all__ = ["MAX_CROPS_REFERENCE", "face_face_rec", "load_detector", "load_model", "non_empty", "pre_process_prediction", "pred_sig",
+__all__ = ["MAX_CROPS_REFERENCE", "MODEL_NAMES", "face_face_rec", "load_detector", "load_model", "model_class", "non_empty", "pre_process_prediction", "pred_sig",
            "pred_tensor", "predict", "predict_on_video", "prediction_accuracy", "read_video", "real_or_fake",
            "write_predictions"]
 

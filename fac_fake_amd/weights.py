@@ -920,3 +920,138 @@ def make_repbn8_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]
         else:
             sd[name] = _synthetic(name, shape, kind, seed)
     return sd
+
+
+# ---------------------------------------------------------------- CViT variants
+# The eight other top-level CViT-main/model/cvit_*.py classes that recombine
+# the parts above (fac_fake_amd/variants.py runs them): the VGG stem as one,
+# two or three nn.Sequentials with plain convs or DEConvs, a GGCA site with
+# x * GGCA(x) or x + GGCA(x), and a LayerNorm or LinearNorm FeedForward PreNorm.
+_VARIANT_BLOCKS = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 256, 4), (256, 512, 4)]   # (cin, cout, convs), pool after
+
+
+def _variant_layers(split, kinds: str, bare26: bool = False):
+    """The stem's layer list in the REPBN8_LAYERS format.  split: blocks per
+    nn.Sequential; kinds: one letter per conv in order, "c" Conv2d or "d"
+    DEConv; bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
+    without BatchNorm or ReLU, a DEConv without BatchNorm (:390-392)."""
+    kinds = kinds.replace(" ", "")
+    names = ["features"] if len(split) == 1 else [f"features{i + 1}" for i in range(len(split))]
+    seq_of = [n for n, cnt in zip(names, split) for _ in range(cnt)]
+    out, k, idx, prev = [], 0, 0, None
+    for bi, (cin, cout, convs) in enumerate(_VARIANT_BLOCKS):
+        seq = seq_of[bi]
+        if seq != prev:
+            idx, prev = 0, seq
+        convs += 1 if bare26 and bi == 2 else 0
+        for li in range(convs):
+            kind = "conv" if kinds[k] == "c" else "deconv"
+            k += 1
+            ci, last = cin if li == 0 else cout, li == convs - 1
+            if bare26 and bi == 2 and li == 2:
+                out.append((seq, idx, kind, ci, cout, None, False, last))
+                idx += 1
+            elif bare26 and bi == 2 and li == 3:
+                out.append((seq, idx, kind, ci, cout, None, True, last))
+                idx += 2
+            else:
+                out.append((seq, idx, kind, ci, cout, idx + 1, True, last))
+                idx += 3
+        idx += 1    # MaxPool2d
+    assert k == len(kinds), (k, kinds)
+    return out
+
+
+_REPBN8_KINDS = "cdd cdd cdcd cddd cddd"
+_PLAIN_KINDS = "ccc ccc ccc cccc cccc"
+_MIXED_KINDS = "ccd cdc cdc cddc cccc"
+# name (the reference file's) -> layers; ggca: None or (site, (C, H, W), op) with
+# site "stem" (after the last sequential) or the sequential it follows and op
+# "mul" (x * GGCA(x)) or "add" (x + GGCA(x)); ff_norm: the FeedForward PreNorm,
+# "layernorm" (eps 1e-5) or "linearnorm" (eval: LayerNorm eps 1e-6, plus its
+# counters and unused RepBN branch in the state_dict); deconv: the unused
+# top-level self.Deconv = DEConv(256) exists.
+VARIANTS = {
+    "cvit_DEConv": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True), ggca=None, ff_norm="linearnorm",
+                        deconv=True),
+    "cvit_GGCA_ADD": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "mul"),
+                          ff_norm="layernorm", deconv=False),
+    "cvit_GGCA_ADD_DEConv": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True),
+                                 ggca=("stem", (512, 7, 7), "mul"), ff_norm="layernorm", deconv=True),
+    "cvit_GGCA_ADD_RepBn": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "add"),
+                                ff_norm="linearnorm", deconv=False),
+    "cvit_GGCA_ADD_DEConv_RepBn": dict(layers=_variant_layers((4, 1), _MIXED_KINDS),
+                                       ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
+    "cvit_GGCA_ADD_DEConv_RepBn3": dict(layers=_variant_layers((2, 2, 1), _MIXED_KINDS),
+                                        ggca=("features1", (64, 56, 56), "add"), ff_norm="linearnorm", deconv=True),
+    "cvit_GGCA_ADD_DEConv_RepBn4": dict(layers=_variant_layers((4, 1), "cdd cdd cdcd cddc ccdc", True),
+                                        ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
+    "cvit_GGCA_ADD_DEConv_RepBn5": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True),
+                                        ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
+}
+VARIANT_NAMES = tuple(VARIANTS)
+
+
+def variant_param_specs(name: str, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
+    """(name, shape, kind) for every key of variant `name`'s state_dict, in the reference's order."""
+    v = VARIANTS[name]
+    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
+    for seq, idx, kind, ci, co, bn, _relu, _pool in v["layers"]:
+        p = f"{seq}.{idx}"
+        if kind == "conv":
+            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
+        else:
+            specs += _deconv_specs(p, co)
+        if bn is not None:
+            specs += _bn_specs(f"{seq}.{bn}", co)
+    pdim = channels * patch_size ** 2
+    specs += [("patch_to_embedding.weight", (dim, pdim), "lin"), ("patch_to_embedding.bias", (dim,), "lbias")]
+    for l in range(depth):
+        p = f"transformer.layers.{l}"
+        specs += [(f"{p}.0.fn.norm.weight", (dim,), "gamma"), (f"{p}.0.fn.norm.bias", (dim,), "beta"),
+                  (f"{p}.0.fn.fn.to_qkv.weight", (3 * dim, dim), "lin"),
+                  (f"{p}.0.fn.fn.to_out.weight", (dim, dim), "lin"), (f"{p}.0.fn.fn.to_out.bias", (dim,), "lbias")]
+        if v["ff_norm"] == "linearnorm":
+            specs += [(f"{p}.1.fn.norm.warm", (), "warm"), (f"{p}.1.fn.norm.iter", (), "step"),
+                      (f"{p}.1.fn.norm.total_step", (), "step"),
+                      (f"{p}.1.fn.norm.norm1.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.norm1.bias", (dim,), "beta"),
+                      (f"{p}.1.fn.norm.norm2.alpha", (1,), "alpha")]
+            specs += _bn_specs(f"{p}.1.fn.norm.norm2.bn", dim)
+        else:
+            specs += [(f"{p}.1.fn.norm.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.bias", (dim,), "beta")]
+        specs += [(f"{p}.1.fn.fn.net.0.weight", (mlp_dim, dim), "lin"), (f"{p}.1.fn.fn.net.0.bias", (mlp_dim,), "lbias"),
+                  (f"{p}.1.fn.fn.net.2.weight", (dim, mlp_dim), "lin"), (f"{p}.1.fn.fn.net.2.bias", (dim,), "lbias")]
+    specs += [("mlp_head.0.weight", (mlp_dim, dim), "lin"), ("mlp_head.0.bias", (mlp_dim,), "lbias"),
+              ("mlp_head.2.weight", (num_classes, mlp_dim), "head"), ("mlp_head.2.bias", (num_classes,), "lbias")]
+    if v["ggca"] is not None:
+        gc = v["ggca"][1][0] // 4               # GGCA(C, H, W): 4 groups, reduction 16
+        specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"),
+                  ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
+        specs += _bn_specs("ggca.shared_conv.1", gc // 16)
+        specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"),
+                  ("ggca.shared_conv.3.bias", (gc,), "cbias")]
+    if v["deconv"]:
+        specs += _deconv_specs("Deconv", 256)   # in the state_dict, never called
+    return specs
+
+
+def make_variant_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights of variant `name`: make_repbn8_state_dict's generator
+    (a key that RepBn8 also has gets the same values for the same seed)."""
+    sd = OrderedDict()
+    for key, shape, kind in variant_param_specs(name, **kw):
+        if kind == "nbt" or kind == "warm":
+            sd[key] = np.array(0, dtype=np.int64)
+        elif kind == "step":
+            sd[key] = np.array(300000, dtype=np.int64)
+        elif kind == "alpha":
+            sd[key] = np.ones(shape, dtype=np.float32)
+        elif kind in ("conv", "dconv"):
+            fan_in = int(np.prod(shape[1:]))
+            a = float(np.sqrt(6.0 / fan_in))
+            if kind == "dconv":
+                a /= 2.8
+            sd[key] = _u(key, shape, seed, -a, a)
+        else:
+            sd[key] = _synthetic(key, shape, kind, seed)
+    return sd

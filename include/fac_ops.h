@@ -280,6 +280,37 @@ size_t fac_kan_scratch_bytes(int rows, int in_f, int out_f);
 int fac_ggca(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
              const float* bn4, const float* w2, const float* b2, void* out, void* stream);
 
+/* GGCA with the caller's combine, for every GGCA site of the CViT variants
+ * (ggca.hip).  x, the weights and att_h / att_w are fac_ggca's; with
+ * g = (x * att_h) * att_w in fp32,
+ *   op 0: out = x * g   (cvit_GGCA_ADD.py, ..._DEConv.py, ..._RepBn8.py)
+ *   op 1: out = x + g   (cvit_GGCA_ADD_RepBn.py, ..._DEConv_RepBn{,3,4,5}.py)
+ * rounded to 16 bits once.  The route depends on (h, w, c, groups) alone
+ * (fac_ggca_apply_route: 1, 2, or 0 for a shape neither takes), so a crop's
+ * output bits do not depend on n or on its place in the batch:
+ *   1 LDS        shapes inside fac_ggca's limits; op 0 is bit-identical to
+ *                fac_ggca.
+ *   2 streaming  every other map with h, w <= 64, cg = c/groups a multiple
+ *                of 16, cg <= 256 and c <= 2048 (cr = cg/16 may be 1):
+ *                pooling (per-row and per-column mean and max), the shared
+ *                MLP + sigmoid on the 2(h + w) pooled vectors of each group,
+ *                element-wise apply.  No atomics, fixed reduction order.  x
+ *                and out must be 16-byte aligned.  The partial results live
+ *                in a library-owned fp32 workspace, one per (device, stream),
+ *                of n * (2h + 2w*ceil(h/16) + h + w) * c floats, allocated
+ *                the first time a stream needs that much and never moved
+ *                afterwards, so later calls allocate nothing and can be
+ *                captured into a graph.  Calls on one stream are ordered;
+ *                calls on different streams use different workspaces.
+ * FAC_ERR_ARG: a null or (route 2) misaligned pointer, a dtype other than
+ * bf16 / fp16, an op other than 0 / 1, n, h, w, c or groups <= 0,
+ * c % groups != 0.  FAC_ERR_SHAPE: a shape outside both routes.
+ * FAC_ERR_OOM: the workspace could not be allocated, or would have to grow
+ * while `stream` is capturing (run the shape once on it before capturing). */
+int fac_ggca_apply_route(int h, int w, int c, int groups);
+int fac_ggca_apply(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
+                   const float* bn4, const float* w2, const float* b2, int op, void* out, void* stream);
+
 /* GCNet context block of CA_S3D_v3 — ContextBlock3d(c, ratio, pooling 'avg',
  * fusion ('channel_add',)), sx_exp_deepfakedetect-master/S3D/new_model/
  * context_block_3d.py:5-88 — on a 16-bit channels-last map x [n][s][c]
