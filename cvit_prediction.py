@@ -70,6 +70,9 @@ def model_class(name: str | None = None):
     if name == "cvit_GGCA_ADD_DEConv_RepBn8":
         from fac_fake_amd.repbn8 import CViT
         return CViT
+    if name == "cvit_GGCA_ADD_DConv":      # not a --model choice: see INTEGRATION.md
+        from fac_fake_amd.dconv import CViT
+        return CViT
     from fac_fake_amd.variants import variant_class
     return variant_class(name)
 
@@ -80,6 +83,8 @@ def _synthetic_state_dict(name: str | None):
         return W.make_state_dict(0)
     if name == "cvit_GGCA_ADD_DEConv_RepBn8":
         return W.make_repbn8_state_dict(0)
+    if name == "cvit_GGCA_ADD_DConv":
+        return W.make_dconv_state_dict(0)
     return W.make_variant_state_dict(name, 0)
 
 

@@ -51,7 +51,8 @@ class VariantCViT(nn.Module):
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        if self.variant not in VARIANTS:
+        table = self._table()
+        if table is None:
             raise TypeError("build a variant with variants.CViT(name) or variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -61,10 +62,9 @@ class VariantCViT(nn.Module):
             raise ValueError(f"dtype must be one of {list(_lib.DTYPES)}")
         self.dtype_name = dtype
         self.patch_size = patch_size
-        self.table = VARIANTS[self.variant]
-        for name, shape, kind in variant_param_specs(self.variant, dim=dim, depth=depth, mlp_dim=mlp_dim,
-                                                     num_classes=num_classes, channels=channels,
-                                                     patch_size=patch_size):
+        self.table = table
+        for name, shape, kind in self._param_specs(dim=dim, depth=depth, mlp_dim=mlp_dim, num_classes=num_classes,
+                                                   channels=channels, patch_size=patch_size):
             *path, leaf = name.split(".")
             mod = self
             for p in path:
@@ -79,6 +79,14 @@ class VariantCViT(nn.Module):
         self._prep = None
         self._ctx = None
         self.eval()
+
+    # what a subclass with another stem replaces (dconv.py): the table, the
+    # state_dict's layout, _prepare_stem and stem_features
+    def _table(self):
+        return VARIANTS.get(self.variant)
+
+    def _param_specs(self, **kw):
+        return variant_param_specs(self.variant, **kw)
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -124,52 +132,71 @@ class VariantCViT(nn.Module):
         if self._prep == (idx, v):
             return
         sd = self.state_dict()
+        self._prepare_stem(sd, device)
+        self._zero = torch.zeros(128, dtype=torch.int16, device=device)   # zero-padding source page
+        self._prepare_ggca(sd, device, self._ggca_after())
+        self._prepare_tail(sd, idx)
+        self._prep = (idx, v)
+
+    def _packed_conv(self, w, H, device):
+        """fac_conv3x3_pack of a folded fp32 weight [co][ci][3][3] (H = 0: the fused block's conv 3->32)."""
         dt = self.dtype_name
         lib = _lib.load()
         dti = _lib.DTYPES[dt]
+        co, ci = w.shape[:2]
+        wf = w.reshape(co, ci, 9).contiguous()
+        if H == 0:
+            out = torch.empty(32 * 64, dtype=torch.int16)
+            _lib.check(lib.fac_stem224_pack_conv1(dti, wf.data_ptr(), out.data_ptr()), None, "pack_conv1")
+        else:
+            n = lib.fac_conv3x3_packed_elems(H, ci, co)
+            if n == 0:
+                raise ValueError(f"conv {ci}->{co} at {H}x{H} is not a fac_conv3x3 shape")
+            out = torch.empty(n, dtype=torch.int16)
+            _lib.check(lib.fac_conv3x3_pack(dti, H, ci, co, wf.data_ptr(), out.data_ptr()), None, "pack_conv3x3")
+        return out.view(TORCH16[dt]).to(device)
 
-        def packed(w, H):
-            co, ci = w.shape[:2]
-            wf = w.reshape(co, ci, 9).contiguous()
-            if H == 0:   # the fused block's conv 3->32
-                out = torch.empty(32 * 64, dtype=torch.int16)
-                _lib.check(lib.fac_stem224_pack_conv1(dti, wf.data_ptr(), out.data_ptr()), None, "pack_conv1")
-            else:
-                n = lib.fac_conv3x3_packed_elems(H, ci, co)
-                if n == 0:
-                    raise ValueError(f"conv {ci}->{co} at {H}x{H} is not a fac_conv3x3 shape")
-                out = torch.empty(n, dtype=torch.int16)
-                _lib.check(lib.fac_conv3x3_pack(dti, H, ci, co, wf.data_ptr(), out.data_ptr()), None, "pack_conv3x3")
-            return out.view(TORCH16[dt]).to(device)
-
+    def _prepare_stem(self, sd, device):
+        """The fused first block's operands (self._stem) and one entry per later conv (self._layers)."""
         layers, H = [], 224
         for i, (w, b, relu, pl) in enumerate(self.folded_layers()):
             co, ci = w.shape[:2]
-            layers.append((packed(w, 0 if i == 0 else H), b.to(device), H, ci, co, pl, relu))
+            layers.append((self._packed_conv(w, 0 if i == 0 else H, device), b.to(device), H, ci, co, pl, relu))
             if pl:
                 H //= 2
         (w1, b1, *_), (w2, b2, *_), (w3, b3, *_) = layers[:3]
         self._stem = (w1, b1, w2, b2, w3, b3)
         self._layers = layers[3:]
-        self._zero = torch.zeros(128, dtype=torch.int16, device=device)   # zero-padding source page
-        # the GGCA site: after how many of self._layers it runs, its shape and op
+
+    def _ggca_after(self):
+        """After how many of self._layers the GGCA combine runs (None: no GGCA)."""
+        if self.table["ggca"] is None:
+            return None
+        site = self.table["ggca"][0]
+        seqs = [l[0] for l in self.table["layers"]]
+        after = len(seqs) if site == "stem" else max(i for i, s in enumerate(seqs) if s == site) + 1
+        return after - 3
+
+    def _prepare_ggca(self, sd, device, after):
+        """self._ggca: the site (index into self._layers), its shape, op and device weights."""
         self._ggca = None
         if self.table["ggca"] is not None:
-            site, chw, op = self.table["ggca"]
-            seqs = [l[0] for l in self.table["layers"]]
-            after = len(seqs) if site == "stem" else max(i for i, s in enumerate(seqs) if s == site) + 1
+            _site, chw, op = self.table["ggca"]
             g = "ggca.shared_conv."
             f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
             cr, cg = sd[g + "0.weight"].shape[:2]
-            self._ggca = (after - 3, chw, GGCA_OPS[op],
+            self._ggca = (after, chw, GGCA_OPS[op],
                           (f32(sd[g + "0.weight"].reshape(cr, cg)), f32(sd[g + "0.bias"]),
                            f32(torch.stack([sd[g + "1.running_mean"], sd[g + "1.running_var"], sd[g + "1.weight"],
                                             sd[g + "1.bias"]])),
                            f32(sd[g + "3.weight"].reshape(cg, cr)), f32(sd[g + "3.bias"])))
-        # the CViT tail (embedding .. head) on a context without a conv stem
+
+    def _prepare_tail(self, sd, idx):
+        """The CViT tail (embedding .. head) on a context without a conv stem."""
+        lib = _lib.load()
         self._release()
         h = ctypes.c_void_p()
-        _lib.check(lib.fac_create(idx, _lib.DTYPES[dt], ctypes.byref(h)), None, "fac_create")
+        _lib.check(lib.fac_create(idx, _lib.DTYPES[self.dtype_name], ctypes.byref(h)), None, "fac_create")
         self._ctx = h
         _lib.check(lib.fac_set_option(h, b"tail_only", 1), h, "fac_set_option")
         _lib.check(lib.fac_set_option(h, b"ffn_ln_eps_exp", FF_LN_EPS_EXP[self.table["ff_norm"]]), h,
@@ -195,7 +222,6 @@ class VariantCViT(nn.Module):
             descs.append(d)
         arr = (_lib.TensorDesc * len(descs))(*descs)
         _lib.check(lib.fac_load_weights(h, ctypes.cast(arr, ctypes.c_void_p), len(descs)), h, "fac_load_weights")
-        self._prep = (idx, v)
 
     def reserve(self, max_batch: int, device=None):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())

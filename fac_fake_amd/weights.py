@@ -1055,3 +1055,66 @@ def make_variant_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str,
         else:
             sd[key] = _synthetic(key, shape, kind, seed)
     return sd
+
+
+# ---------------------------------------------------------------- CViT GGCA_ADD_DConv
+# CViT-main/model/cvit_GGCA_ADD_DConv.py::CViT (:180-299): the base CViT's one
+# `features` Sequential with nine of its 3x3 convs replaced by
+# InceptionDWConv2d(C) (:157-177: 5C/8 channels pass, then C/8 each through a
+# depthwise 3x3, 1x11 and 11x1 conv, all with bias), x + GGCA(x) on the
+# 512x7x7 map and the base CViT's tail (plain LayerNorm in both PreNorms).
+# One entry per conv / InceptionDWConv2d, the Sequential indices being the base
+# CViT's:  (index, kind "conv" | "idw", cin, cout, bn index, pool after)
+DCONV_KINDS = "cii cii cii ciii cccc"
+DCONV_LAYERS = [(ci_, "conv" if k == "c" else "idw", cin, cout, bi_, i in POOL_AFTER)
+                for i, (k, (cin, cout), (ci_, bi_)) in enumerate(zip(DCONV_KINDS.replace(" ", ""), STEM_CHANNELS,
+                                                                      stem_module_indices()))]
+IDW_BAND = 11
+# the depthwise taps are drawn in (-0.5a, 1.5a), a = gain * sqrt(3 / taps): both signs with a positive sum, so
+# the conv channels keep about the scale of the identity channels beside them (tools/make_golden_dconv.py
+# asserts that the fixture crops' probabilities stay away from 0 and 1)
+DCONV_DW_GAIN = 0.35
+
+
+def _idw_specs(p, c):
+    gc = c // 8
+    return [(f"{p}.dwconv_hw.weight", (gc, 1, 3, 3), "dw"), (f"{p}.dwconv_hw.bias", (gc,), "cbias"),
+            (f"{p}.dwconv_w.weight", (gc, 1, 1, IDW_BAND), "dw"), (f"{p}.dwconv_w.bias", (gc,), "cbias"),
+            (f"{p}.dwconv_h.weight", (gc, 1, IDW_BAND, 1), "dw"), (f"{p}.dwconv_h.bias", (gc,), "cbias")]
+
+
+def dconv_param_specs(dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
+    """(name, shape, kind) for every key of cvit_GGCA_ADD_DConv.CViT's state_dict, in its order (238 keys)."""
+    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
+    for idx, kind, ci, co, bn, _pool in DCONV_LAYERS:
+        p = f"features.{idx}"
+        if kind == "conv":
+            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
+        else:
+            specs += _idw_specs(p, co)
+        specs += _bn_specs(f"features.{bn}", co)
+    specs += [s for s in cvit_param_specs(dim, depth, mlp_dim, num_classes, channels, patch_size)
+              if not s[0].startswith("features.") and s[0] not in ("pos_embedding", "cls_token")]
+    gc = 512 // 4                           # GGCA(512, 7, 7): 4 groups, reduction 16
+    specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"), ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
+    specs += _bn_specs("ggca.shared_conv.1", gc // 16)
+    specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"), ("ggca.shared_conv.3.bias", (gc,), "cbias")]
+    return specs
+
+
+def make_dconv_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic cvit_GGCA_ADD_DConv weights (same generator; a key the base
+    CViT or a variant also has gets the same values for the same seed)."""
+    sd = OrderedDict()
+    for key, shape, kind in dconv_param_specs(**kw):
+        if kind == "nbt":
+            sd[key] = np.array(0, dtype=np.int64)
+        elif kind == "conv":
+            a = float(np.sqrt(6.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "dw":
+            a = float(DCONV_DW_GAIN * np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -0.5 * a, 1.5 * a)
+        else:
+            sd[key] = _synthetic(key, shape, kind, seed)
+    return sd

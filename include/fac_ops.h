@@ -462,6 +462,29 @@ int fac_conv3x3_res(int dtype, const void* in, const void* wpk, const float* bia
  * s < 1, c < 8 or c % 8 != 0. */
 int fac_avgpool_f32(int dtype, const void* x, int n, int s, int c, float* y, void* stream);
 
+/* InceptionDWConv2d -> BatchNorm2d (eval) -> ReLU (-> MaxPool2d(2,2) if pool)
+ * of CViT-main/model/cvit_GGCA_ADD_DConv.py:157-177 in one launch
+ * (idwconv.hip).  in [n][h][w][c] -> out [n][h'][w'][c] (h' = h/2, w' = w/2
+ * with pool), 16-bit channels-last, 16-byte aligned.  With gc = c/8:
+ *   channels [0, c - 3gc)   y = in
+ *   the next gc             y = depthwise 3x3, padding 1     w_hw [gc][3][3]
+ *   the next gc             y = depthwise 1x11 along w, padding 5   w_w [gc][11]
+ *   the last gc             y = depthwise 11x1 along h, padding 5   w_h [gc][11]
+ *   out = maxpool?(relu(scale[c] * y + shift[c]))
+ * Taps, scale and shift are fp32 device arrays.  The taps are used as given
+ * (not pre-multiplied by scale): y is an fp32 fma chain over the taps in index
+ * order, taps outside the map are skipped (zero padding of the conv's input:
+ * they contribute 0, not shift), then fma(scale, y, shift), ReLU, the window
+ * max, and the only rounding, at the store.  The caller folds the conv bias
+ * and the BatchNorm: scale = gamma / sqrt(var + eps), shift = beta - mean *
+ * scale (+ bias * scale on the 3gc conv channels).  A crop's output does not
+ * depend on n.
+ * FAC_ERR_ARG: a null or misaligned pointer, a bad dtype, n <= 0;
+ * FAC_ERR_SHAPE: c no multiple of 32 or outside 32..256, h or w outside
+ * 1..224, odd h or w with pool. */
+int fac_idwconv(int dtype, const void* in, void* out, int n, int h, int w, int c, const float* w_hw, const float* w_w,
+                const float* w_h, const float* scale, const float* shift, int pool, void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
