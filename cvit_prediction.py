@@ -73,6 +73,10 @@ def model_class(name: str | None = None):
     if name == "cvit_GGCA_ADD_DConv":      # not a --model choice: see INTEGRATION.md
         from fac_fake_amd.dconv import CViT
         return CViT
+    from fac_fake_amd.weights import OTHER_NAMES
+    if name in OTHER_NAMES:                # model/other/<name>.py; not --model choices either
+        from fac_fake_amd.other import other_class
+        return other_class(name)
     from fac_fake_amd.variants import variant_class
     return variant_class(name)
 
@@ -85,6 +89,8 @@ def _synthetic_state_dict(name: str | None):
         return W.make_repbn8_state_dict(0)
     if name == "cvit_GGCA_ADD_DConv":
         return W.make_dconv_state_dict(0)
+    if name in W.OTHER_NAMES:
+        return W.make_other_state_dict(name, 0)
     return W.make_variant_state_dict(name, 0)
 
 

@@ -6,6 +6,8 @@
 //                 per channel group
 //   g           = (x * att_h) * att_w                  (the reference's order)
 //   out         = op == 0 ? x * g : x + g              (one 16-bit rounding)
+//                 fac_ggca_scale (LDS route only): out = g, the module's own
+//                 output, for the classes that assign x = GGCA(x)
 //
 // on 16-bit channels-last maps x [n][h][w][c], fp32 in between.  Two routes,
 // chosen from (h, w, c, groups) alone so that a crop's bits never depend on
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(256) void ggca_lds_k(const uint16_t* __restrict__ x
     const float aw = 1.0f / (1.0f + expf(-(pv[(2 * H + xx) * CG + c] + pv[(2 * H + W + xx) * CG + c])));
     const float v = xs[i];
     if (OP == 0) ob[(size_t)pix * C + c] = T::from_f32(v * ((v * ah) * aw));
-    else ob[(size_t)pix * C + c] = T::from_f32(v + (v * ah) * aw);
+    else if (OP == 1) ob[(size_t)pix * C + c] = T::from_f32(v + (v * ah) * aw);
+    else ob[(size_t)pix * C + c] = T::from_f32((v * ah) * aw);   // fac_ggca_scale: GGCA(x) itself
   }
 }
 
@@ -398,6 +401,22 @@ int fac_ggca_apply(int dtype, const void* x, int n, int h, int w, int c, int gro
     if (op == 0) ggca_apply_k<F16, 0><<<n * bpi, GG_T, 0, st>>>(xi, h, w, cv, bpi, ws, xo);
     else ggca_apply_k<F16, 1><<<n * bpi, GG_T, 0, st>>>(xi, h, w, cv, bpi, ws, xo);
   }
+  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+}
+
+// GGCA(x) alone, out = (x * att_h) * att_w: the LDS route with no combine.
+int fac_ggca_scale(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
+                   const float* bn4, const float* w2, const float* b2, void* out, void* stream) {
+  using namespace fac;
+  if (!x || !out || !w1 || !b1 || !bn4 || !w2 || !b2 || n <= 0 || h <= 0 || w <= 0 || c <= 0 || groups <= 0 ||
+      c % groups || (dtype != FAC_DTYPE_BF16 && dtype != FAC_DTYPE_F16))
+    return FAC_ERR_ARG;
+  if (fac_ggca_apply_route(h, w, c, groups) != 1 || (long long)n * groups > 0x7fffffffLL) return FAC_ERR_SHAPE;
+  const hipStream_t st = (hipStream_t)stream;
+  const uint16_t* xi = (const uint16_t*)x;
+  uint16_t* xo = (uint16_t*)out;
+  if (dtype == FAC_DTYPE_BF16) ggca_lds_k<BF16, 2><<<n * groups, 256, 0, st>>>(xi, h, w, c, groups, w1, b1, bn4, w2, b2, xo);
+  else ggca_lds_k<F16, 2><<<n * groups, 256, 0, st>>>(xi, h, w, c, groups, w1, b1, bn4, w2, b2, xo);
   return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
 }
 

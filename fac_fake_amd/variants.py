@@ -47,6 +47,7 @@ class VariantCViT(nn.Module):
     """One CViT variant on gfx950 (inference); subclasses set ``variant``."""
 
     variant: str = ""
+    ggca_ops = GGCA_OPS          # table op name -> what ggca_combine16 dispatches on (other.py adds one)
 
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
@@ -185,7 +186,7 @@ class VariantCViT(nn.Module):
             g = "ggca.shared_conv."
             f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
             cr, cg = sd[g + "0.weight"].shape[:2]
-            self._ggca = (after, chw, GGCA_OPS[op],
+            self._ggca = (after, chw, self.ggca_ops[op],
                           (f32(sd[g + "0.weight"].reshape(cr, cg)), f32(sd[g + "0.bias"]),
                            f32(torch.stack([sd[g + "1.running_mean"], sd[g + "1.running_var"], sd[g + "1.weight"],
                                             sd[g + "1.bias"]])),

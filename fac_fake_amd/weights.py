@@ -994,7 +994,11 @@ VARIANT_NAMES = tuple(VARIANTS)
 
 def variant_param_specs(name: str, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
     """(name, shape, kind) for every key of variant `name`'s state_dict, in the reference's order."""
-    v = VARIANTS[name]
+    return _table_param_specs(VARIANTS[name], dim, depth, mlp_dim, num_classes, channels, patch_size)
+
+
+def _table_param_specs(v, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
+    """variant_param_specs for one table entry (VARIANTS' or OTHER_VARIANTS')."""
     specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
     for seq, idx, kind, ci, co, bn, _relu, _pool in v["layers"]:
         p = f"{seq}.{idx}"
@@ -1115,6 +1119,94 @@ def make_dconv_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]"
         elif kind == "dw":
             a = float(DCONV_DW_GAIN * np.sqrt(3.0 / int(np.prod(shape[1:]))))
             sd[key] = _u(key, shape, seed, -0.5 * a, 1.5 * a)
+        else:
+            sd[key] = _synthetic(key, shape, kind, seed)
+    return sd
+
+
+# ---------------------------------------------------------------- CViT model/other/
+# Four classes of CViT-main/model/other/ that keep the CViT's channel / pool
+# plan, patch and tail (fac_fake_amd/other.py runs them).  The entries have
+# VARIANTS' format (plain convs, LayerNorm in both PreNorms) plus `smfa`: None,
+# or the sequential that x + SMFA(x) follows, and a third GGCA op, "att": x = GGCA(x), the module's own
+# output x * att_h * att_w (VARIANTS' "mul" is x * GGCA(x)).  cvit_GGCA_SMFA has GGCA on the
+# stem output AND the SMFA block (:160-203) on the 256x14x14 map.
+OTHER_VARIANTS = {
+    "cvit_GGCA": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "att"),
+                      ff_norm="layernorm", deconv=False, smfa=None),
+    "cvit_GGCA4": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("features1", (256, 14, 14), "att"),
+                       ff_norm="layernorm", deconv=False, smfa=None),
+    "cvit_GGCA_ADD3": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("features1", (256, 14, 14), "add"),
+                           ff_norm="layernorm", deconv=False, smfa=None),
+    "cvit_GGCA_SMFA": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "add"),
+                           ff_norm="layernorm", deconv=False, smfa="features1"),
+}
+OTHER_NAMES = tuple(OTHER_VARIANTS)
+SMFA_DIM = 256
+# Synthetic SMFA weights.  The reference initialises alpha = 1 and belt = 0, which hides the variance path;
+# here alpha is drawn in +-[0.5, 1.5] and belt in +-[0.5, 1.5] * SMFA_BELT_GAIN.  The block's 1x1 convs are
+# He-uniform times a gain, the two depthwise convs have taps and biases of both signs.  The gains are
+# tuned so that, on the 4 golden crops, the block is comparable to its input (||SMFA(f)|| / ||f|| within
+# 0.25..4), the variance term is at least a tenth of the max term in u, the gate takes both signs and no
+# probability saturates; tools/make_golden_other.py asserts all four.
+SMFA_BELT_GAIN = 1.0
+SMFA_GAINS = {"linear_0": 1.0, "linear_1": 1.5, "linear_2": 1.0, "lde.conv_0.1": 1.0, "lde.conv_1": 1.0}
+SMFA_DW_TAP = 0.6          # dw_conv / lde.conv_0.0 taps in +-SMFA_DW_TAP
+SMFA_DW_BIAS = 0.3         # and their biases in +-SMFA_DW_BIAS
+
+
+def _smfa_specs(p, c):
+    specs = [(f"{p}.alpha", (1, c, 1, 1), "smfa_alpha"), (f"{p}.belt", (1, c, 1, 1), "smfa_belt")]
+    for name, co, ci in (("linear_0", 2 * c, c), ("linear_1", c, c), ("linear_2", c, c)):
+        specs += [(f"{p}.{name}.weight", (co, ci, 1, 1), "smfa_pw"), (f"{p}.{name}.bias", (co,), "smfa_pwb")]
+    specs += [(f"{p}.lde.conv_0.0.weight", (2 * c, 1, 3, 3), "smfa_dw"), (f"{p}.lde.conv_0.0.bias", (2 * c,), "smfa_dwb"),
+              (f"{p}.lde.conv_0.1.weight", (2 * c, 2 * c, 1, 1), "smfa_pw"), (f"{p}.lde.conv_0.1.bias", (2 * c,), "smfa_pwb"),
+              (f"{p}.lde.conv_1.weight", (c, 2 * c, 1, 1), "smfa_pw"), (f"{p}.lde.conv_1.bias", (c,), "smfa_pwb"),
+              (f"{p}.dw_conv.weight", (c, 1, 3, 3), "smfa_dw"), (f"{p}.dw_conv.bias", (c,), "smfa_dwb")]
+    return specs
+
+
+def other_param_specs(name: str, **kw):
+    """(name, shape, kind) for every key of model/other/<name>.py's CViT, in its order (202; SMFA: 218)."""
+    v = OTHER_VARIANTS[name]
+    specs = _table_param_specs(v, **kw)
+    if v["smfa"] is not None:
+        specs += _smfa_specs("smfa", SMFA_DIM)
+    return specs
+
+
+def _signed(name, shape, seed, lo, hi):
+    """Magnitudes in [lo, hi) with a random sign."""
+    u = uniform(name, int(np.prod(shape)), seed)
+    mag = np.float32(lo) + np.float32(hi - lo) * np.abs(u)
+    return (np.where(u < 0, -mag, mag)).astype(np.float32).reshape(shape)
+
+
+def make_other_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights of model/other/<name>.py (make_variant_state_dict's
+    generator: a key another CViT also has gets the same values for the same
+    seed; the SMFA block's scheme is described at SMFA_GAINS)."""
+    sd = OrderedDict()
+    for key, shape, kind in other_param_specs(name, **kw):
+        if kind == "nbt":
+            sd[key] = np.array(0, dtype=np.int64)
+        elif kind == "conv":
+            a = float(np.sqrt(6.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "smfa_pw":
+            gain = SMFA_GAINS[key[len("smfa."):-len(".weight")]]
+            a = float(gain * np.sqrt(3.0 / shape[1]))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "smfa_pwb":
+            sd[key] = _u(key, shape, seed, -0.1, 0.1)
+        elif kind == "smfa_dw":
+            sd[key] = _u(key, shape, seed, -SMFA_DW_TAP, SMFA_DW_TAP)
+        elif kind == "smfa_dwb":
+            sd[key] = _u(key, shape, seed, -SMFA_DW_BIAS, SMFA_DW_BIAS)
+        elif kind == "smfa_alpha":
+            sd[key] = _signed(key, shape, seed, 0.5, 1.5)
+        elif kind == "smfa_belt":
+            sd[key] = _signed(key, shape, seed, 0.5 * SMFA_BELT_GAIN, 1.5 * SMFA_BELT_GAIN)
         else:
             sd[key] = _synthetic(key, shape, kind, seed)
     return sd

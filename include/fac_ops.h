@@ -311,6 +311,14 @@ int fac_ggca_apply_route(int h, int w, int c, int groups);
 int fac_ggca_apply(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
                    const float* bn4, const float* w2, const float* b2, int op, void* out, void* stream);
 
+/* GGCA(x) itself, out = (x * att_h) * att_w rounded once, for the classes
+ * that assign x = GGCA(x) (CViT-main/model/other/cvit_GGCA.py, cvit_GGCA4.py).
+ * fac_ggca_apply's LDS route with no combine: its arguments, FAC_ERR_ARG as
+ * there, FAC_ERR_SHAPE for a shape outside that route
+ * (fac_ggca_apply_route(h, w, c, groups) != 1). */
+int fac_ggca_scale(int dtype, const void* x, int n, int h, int w, int c, int groups, const float* w1, const float* b1,
+                   const float* bn4, const float* w2, const float* b2, void* out, void* stream);
+
 /* GCNet context block of CA_S3D_v3 — ContextBlock3d(c, ratio, pooling 'avg',
  * fusion ('channel_add',)), sx_exp_deepfakedetect-master/S3D/new_model/
  * context_block_3d.py:5-88 — on a 16-bit channels-last map x [n][s][c]
@@ -484,6 +492,37 @@ int fac_avgpool_f32(int dtype, const void* x, int n, int s, int c, float* y, voi
  * 1..224, odd h or w with pool. */
 int fac_idwconv(int dtype, const void* in, void* out, int n, int h, int w, int c, const float* w_hw, const float* w_w,
                 const float* w_h, const float* scale, const float* shift, int pool, void* stream);
+
+/* SMFA(x) or x + SMFA(x) of CViT-main/model/other/cvit_GGCA_SMFA.py:160-203
+ * (smfa.hip) on a 16-bit channels-last map x [n][h][w][c] -> out [n][h][w][c],
+ * for 8 <= h, w <= 15, where the block's adaptive max-pool is the per-channel
+ * global max.  With t = linear_0(x), y = t[:, :c], xx = t[:, c:]:
+ *   u    = alpha * (cw * max_p xx + cb) + belt * var_p xx    (unbiased variance)
+ *   g    = GELU(w1 u + b1)                                    fp32, [n][c]
+ *   hmap = GELU(wpw dw3x3(y) + bpw)     depthwise 3x3, zero padding, output j
+ *                                       reads y channel j / 2, + dwb
+ *   out  = [x +] wcat [xx * g | hmap] + bcat
+ * fac_smfa_pack (host pointers, fp32 in) writes fac_smfa_packed_bytes(c) bytes:
+ * w0 [2c][c], b0 [2c]; gate4 [4][c] = alpha, cw, cb, belt (cw, cb: dw_conv's
+ * centre tap and bias); w1 [c][c], b1 [c]; dww [2c][9], dwb [2c]; wpw [2c][2c],
+ * bpw [2c]; wcat [c][3c] = [linear_2.W | linear_2.W conv_1.W], bcat [c].  w0,
+ * wpw and wcat become 16-bit MFMA operands, the rest stays fp32.  wpk is that
+ * blob in device memory.  gate_out: an optional fp32 [n][c] copy of g.
+ * scratch: fac_smfa_scratch_bytes(n, h, w, c) bytes (0 for a bad shape); the
+ * call allocates nothing, runs four launches on `stream` and can be captured.
+ * Rounding: t, the depthwise operand, hmap, the xx * g operand and the output
+ * are rounded to 16 bits, the statistics are taken from the stored xx; every
+ * sum is fp32 in a fixed order, so a crop's output does not depend on n.
+ * FAC_ERR_ARG: a null (x, wpk, out, scratch) or misaligned (16 bytes) pointer,
+ * n <= 0, a bad dtype; FAC_ERR_SHAPE: h or w outside 8..15, c no multiple of
+ * 64 or above 256. */
+size_t fac_smfa_scratch_bytes(int n, int h, int w, int c);
+size_t fac_smfa_packed_bytes(int c);
+int fac_smfa_pack(int dtype, int c, const float* w0, const float* b0, const float* gate4, const float* w1,
+                  const float* b1, const float* dww, const float* dwb, const float* wpw, const float* bpw,
+                  const float* wcat, const float* bcat, void* out);
+int fac_smfa(int dtype, const void* x, int n, int h, int w, int c, const void* wpk, int residual, void* out,
+             float* gate_out, void* scratch, void* stream);
 
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
