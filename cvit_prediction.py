@@ -67,16 +67,8 @@ def model_class(name: str | None = None):
     if name in (None, "cvit"):
         from fac_fake_amd.cvit import CViT
         return CViT
-    if name == "cvit_GGCA_ADD_DEConv_RepBn8":
-        from fac_fake_amd.repbn8 import CViT
-        return CViT
-    if name == "cvit_GGCA_ADD_DConv":      # not a --model choice: see INTEGRATION.md
-        from fac_fake_amd.dconv import CViT
-        return CViT
-    from fac_fake_amd.weights import OTHER_NAMES
-    if name in OTHER_NAMES:                # model/other/<name>.py; not --model choices either
-        from fac_fake_amd.other import other_class
-        return other_class(name)
+    # weights.CVIT_FAMILY's names; cvit_GGCA_ADD_DConv and the model/other/ ones
+    # are not --model choices: see INTEGRATION.md
     from fac_fake_amd.variants import variant_class
     return variant_class(name)
 
@@ -85,13 +77,7 @@ def _synthetic_state_dict(name: str | None):
     from fac_fake_amd import weights as W
     if name in (None, "cvit"):
         return W.make_state_dict(0)
-    if name == "cvit_GGCA_ADD_DEConv_RepBn8":
-        return W.make_repbn8_state_dict(0)
-    if name == "cvit_GGCA_ADD_DConv":
-        return W.make_dconv_state_dict(0)
-    if name in W.OTHER_NAMES:
-        return W.make_other_state_dict(name, 0)
-    return W.make_variant_state_dict(name, 0)
+    return W.make_family_state_dict(name, 0)
 
 
 def load_model(weights: str | None = None, dtype: str = "fp16", dev: str | None = None, name: str | None = None):

@@ -1,60 +1,200 @@
-"""Drop-ins for eight more ``CViT-main/model/cvit_*.py`` classes on gfx950 HIP kernels.
+"""Drop-ins for fourteen ``CViT-main/model/**/cvit_*.py`` classes on gfx950 HIP kernels.
 
-``cvit_DEConv``, ``cvit_GGCA_ADD``, ``cvit_GGCA_ADD_DEConv``,
-``cvit_GGCA_ADD_RepBn`` and ``cvit_GGCA_ADD_DEConv_RepBn{,3,4,5}`` recombine
-the parts of ``repbn8.CViT``; what differs is data, one ``VARIANTS`` entry each
-(fac_fake_amd/weights.py, beside ``REPBN8_LAYERS`` whose format its layer lists
-share):
+RepBn8, the eight of ``weights.VARIANTS``, ``cvit_GGCA_ADD_DConv`` and the four
+of ``weights.OTHER_VARIANTS`` keep the CViT's channel / pool plan, the single
+7x7 patch, the 2-token tail and the batch-slot ``pos_embedding`` rule; what
+differs is data, one ``weights.CVIT_FAMILY`` entry each (its format is described
+there).  ``VariantCViT`` is the one class body for all of them:
 
-* the conv stem: one, two or three ``nn.Sequential``s of plain convs and
-  DEConvs.  Every variant keeps the CViT's channel / pool plan, so the first
-  block (three convs + pool, DEConvs folded) is the fused ``fac_stem224`` kernel
-  and every later conv one ``fac_conv3x3`` launch, as in repbn8.py;
-* the GGCA site: none (``cvit_DEConv``), the 512x7x7 stem output, or — RepBn3 —
-  the 64x56x56 map after ``features1``; and its combine, ``x * GGCA(x)`` or
-  ``x + GGCA(x)``.  Both are one ``fac_ggca_apply`` call (ggca.hip: LDS-resident
-  on 7x7, the streaming pool / MLP / apply path on 56x56);
-* the FeedForward PreNorm: ``nn.LayerNorm`` (eps 1e-5) or LinearNorm, whose
-  eval branch is LayerNorm(eps 1e-6) — the tail context's ``ffn_ln_eps_exp``;
-* whether the unused top-level ``Deconv`` is in the state_dict.
+* the conv stem is compiled from the entry into a flat list of launches
+  (``stem_plan``, a function of the entry alone; ``_prepare_stem`` adds the
+  device operands) that ``stem_features`` walks:
+
+    stem224  ``fac_stem224``, the fused first block (three convs + pool, DEConvs
+             folded, the input normalisation), where the entry's first three
+             layers are convs or DEConvs;
+    pack32   otherwise ``fac_pack_input`` to 32 channels (zeros beyond 3, so the
+             first conv's zero padding lands in normalised space; that conv's
+             folded weight is zero beyond input channel 3);
+    conv     ``fac_conv3x3``: every other conv, DEConvs and eval BatchNorm
+             folded on the host, the 2x2 max-pool and the ReLU in its epilogue;
+    idw      ``fac_idwconv``: InceptionDWConv2d -> BatchNorm -> ReLU (-> pool);
+    smfa     ``fac_smfa``: x + SMFA(x), with a scratch buffer kept per model;
+    ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
+             (GGCA(x)) at the entry's site;
+
+* the tail (embedding .. head) is ``fac_forward_features`` on a "tail_only"
+  context, the FeedForward PreNorm ``nn.LayerNorm`` (eps 1e-5) or LinearNorm,
+  whose eval branch is LayerNorm(eps 1e-6) — the context's ``ffn_ln_eps_exp``.
 
 Each class has the reference's constructor, ``state_dict`` (keys, shapes,
-order), batch-slot ``pos_embedding`` rule and ``forward(img, mask=None)``, plus
-``forward_u8`` / ``reserve`` / inference-only ``train()`` exactly as
-``repbn8.CViT``; there is no CPU fallback.  ``CViT(name, ...)`` builds one by
-the reference file's name, ``variant_class(name)`` gives the class (what the
-``model/<name>.py`` shims export).  Grad-CAM is not implemented for these.
+order) and ``forward(img, mask=None)``, plus ``forward_u8`` / ``reserve`` and an
+inference-only ``train()``; there is no CPU fallback.  The whole forward is
+stream-ordered on the current torch stream and can be captured into a hipGraph.
+``variant_class(name)`` gives the class the ``model/<name>.py`` shims export;
+``CViT(name, ...)`` builds one of the eight ``VARIANTS``.  Grad-CAM exists for
+RepBn8 only (repbn8.py).
+
+To add a variant: add its entry to a table in weights.py; add a step kind here
+(a ``stem_plan`` line, its operands in ``_prepare_stem``, a ``_step_<kind>``
+method) only if it brings a new kernel.
 """
 from __future__ import annotations
 
 import ctypes
+import importlib
+from collections import namedtuple
 
 import torch
 from torch import nn
 
 from . import _lib
-from .cvit import _Node, reference_mask_poisons, weight_versions
-from .ops import TORCH16, fold_bn
-from .repbn8 import _BUFFERS, BN_EPS, SUPPORTED, _init_tensor, _pos_index, deconv_fold
-from .weights import VARIANT_NAMES, VARIANTS, variant_param_specs
+from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
+from .ops import TORCH16, fold_bn, pack_input
+from .weights import CVIT_FAMILY, FAMILY_NAMES, REPBN8_NAME, VARIANT_NAMES, VARIANTS, param_specs
 
+SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
+                 mlp_dim=2048)
+BN_EPS = 1e-5
+MEAN = (0.485, 0.456, 0.406)     # cvit_prediction.py:41
+STD = (0.229, 0.224, 0.225)      # cvit_prediction.py:42
 GGCA_GROUPS = 4
-GGCA_OPS = {"mul": 0, "add": 1}          # fac_ggca_apply's op
+GGCA_OPS = {"mul": 0, "add": 1, "att": 2}    # fac_ggca_apply's op; 2: fac_ggca_scale
+GGCA_ATT = GGCA_OPS["att"]
 FF_LN_EPS_EXP = {"layernorm": 5, "linearnorm": 6}
+_BUFFERS = ("rmean", "rvar", "nbt", "warm", "step")
+
+
+def deconv_fold(sd, p: str):
+    """DEConv.forward's effective 3x3 weight and bias (cvit_GGCA_ADD_DEConv_RepBn8.py:329-338):
+    the sum of Conv2d_cd (:221-228), Conv2d_hd (:292-297), Conv2d_vd (:310-315),
+    Conv2d_ad with theta 1 (:242-246) and the plain conv1_5, evaluated with
+    the reference's tensor ops in its order, in fp32 on the CPU."""
+    f = lambda k: sd[f"{p}.{k}"].detach().to("cpu", torch.float32)  # noqa: E731
+    w1 = f("conv1_1.conv.weight")
+    o, i = w1.shape[:2]
+    t = w1.reshape(o, i, 9)
+    cd = torch.zeros(o, i, 9)
+    cd[:, :, :] = t[:, :, :]
+    cd[:, :, 4] = t[:, :, 4] - t[:, :, :].sum(2)
+    h = f("conv1_2.conv.weight")
+    hd = torch.zeros(o, i, 9)
+    hd[:, :, [0, 3, 6]] = h[:, :, :]
+    hd[:, :, [2, 5, 8]] = -h[:, :, :]
+    v = f("conv1_3.conv.weight")
+    vd = torch.zeros(o, i, 9)
+    vd[:, :, [0, 1, 2]] = v[:, :, :]
+    vd[:, :, [6, 7, 8]] = -v[:, :, :]
+    a = f("conv1_4.conv.weight").reshape(o, i, 9)
+    ad = a - 1.0 * a[:, :, [3, 0, 1, 6, 4, 2, 7, 8, 5]]
+    w = (cd.reshape(o, i, 3, 3) + hd.reshape(o, i, 3, 3) + vd.reshape(o, i, 3, 3) + ad.reshape(o, i, 3, 3)
+         + f("conv1_5.weight"))
+    b = f("conv1_1.conv.bias") + f("conv1_2.conv.bias") + f("conv1_3.conv.bias") + f("conv1_4.conv.bias") + \
+        f("conv1_5.bias")
+    return w, b
+
+
+def _init_tensor(shape, kind):
+    if kind in ("nbt", "warm"):
+        return torch.zeros((), dtype=torch.long)
+    if kind == "step":
+        return torch.tensor(300000)
+    if kind in ("rmean", "beta", "lbias", "cbias"):
+        return torch.zeros(shape)
+    if kind in ("rvar", "gamma", "alpha"):
+        return torch.ones(shape)
+    if kind == "emb":
+        return torch.randn(shape)
+    t = torch.empty(shape)
+    fan_in = 1
+    for s in shape[1:]:
+        fan_in *= s
+    return t.uniform_(-1.0 / fan_in ** 0.5, 1.0 / fan_in ** 0.5)
+
+
+def _pos_index(B: int, pos_index, device) -> torch.Tensor:
+    if pos_index is None:
+        if B > MAX_SLOTS:   # `x += self.pos_embedding[0:shape]` raises past 32
+            raise RuntimeError(f"The size of tensor a ({B}) must match the size of tensor b ({MAX_SLOTS}) "
+                               f"at non-singleton dimension 0")
+        return torch.arange(B, dtype=torch.int32, device=device)
+    p = torch.as_tensor(pos_index)
+    if p.shape != (B,):
+        raise ValueError(f"pos_index must have shape ({B},), got {tuple(p.shape)}")
+    if p.numel() and not torch.cuda.is_current_stream_capturing() and (int(p.min()) < 0 or int(p.max()) >= MAX_SLOTS):
+        raise IndexError(f"pos_index values must lie in [0, {MAX_SLOTS})")
+    return p.to(device=device, dtype=torch.int32).contiguous()
+
+
+# One launch of the stem.  labels: the values of stem_features' `upto` that stop
+# right after it ("after n entries of the table's layers", "features1", "smfa",
+# "ggca"); H: the side of the map it runs on; ci, co: its input / output channels;
+# pool, relu: fac_conv3x3's and fac_idwconv's epilogue; op: the ggca step's GGCA_OPS name.
+Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, False, None))
+
+
+def stem_plan(entry) -> list:
+    """The launches of one CVIT_FAMILY entry's conv stem, in order (kinds: the
+    module docstring's).  The first block is the fused stem224 if and only if
+    the entry's first three layers are convs or DEConvs."""
+    layers = entry["layers"]
+    seqs = [l[0] for l in layers]
+    end = lambda s: len(layers) if s == "stem" else max(i for i, q in enumerate(seqs) if q == s) + 1  # noqa: E731
+    ggca_at = end(entry["ggca"][0]) if entry["ggca"] is not None else None
+    smfa_at = end(entry["smfa"]) if entry["smfa"] is not None else None
+    f1 = end(seqs[0])
+    fused = all(l[2] != "idw" for l in layers[:3])
+    if fused:
+        assert [l[3:5] + l[6:] for l in layers[:3]] == [(3, 32, True, False), (32, 32, True, False),
+                                                         (32, 32, True, True)] and min(f1, ggca_at or 4, smfa_at or 4) > 3
+        plan, H, done = [Step("stem224", (3,), 224, 3, 32, True, True)], 112, 3
+    else:
+        plan, H, done = [Step("pack32", (), 224, 3, 32)], 224, 0
+    for n, (_seq, _idx, kind, ci, co, _bn, relu, pool) in enumerate(layers[done:], done + 1):
+        labels = (n, "features1") if n == f1 else (n,)
+        if kind == "idw":
+            plan.append(Step("idw", labels, H, co, co, pool, True))
+        else:
+            plan.append(Step("conv", labels, H, 32 if n == 1 else ci, co, pool, relu))
+        if pool:
+            H //= 2
+        if n == smfa_at:
+            plan.append(Step("smfa", ("smfa",), H, co, co))
+        if n == ggca_at:
+            C, Hg, _W = entry["ggca"][1]
+            plan.append(Step("ggca", ("ggca",), Hg, C, C, op=entry["ggca"][2]))
+    return plan
+
+
+def steps_upto(plan, upto) -> int:
+    """How many steps of `plan` run for stem_features' `upto`: None all of them;
+    an int n up to and including the n-th entry of the table's layers;
+    "features1" the first sequential, before the block that follows it; "smfa" /
+    "ggca" that combine.  ValueError where the plan has no such stop: an int
+    inside the fused first block or past the last layer, a block the class lacks."""
+    if upto is None:
+        return len(plan)
+    for i, s in enumerate(plan, 1):
+        if upto in s.labels:
+            return i
+    raise ValueError(f"this stem has no stop {upto!r}; it has {[l for s in plan for l in s.labels]}")
 
 
 class VariantCViT(nn.Module):
     """One CViT variant on gfx950 (inference); subclasses set ``variant``."""
 
     variant: str = ""
-    ggca_ops = GGCA_OPS          # table op name -> what ggca_combine16 dispatches on (other.py adds one)
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        if cls.__dict__.get("variant"):
+            _CLASSES[cls.variant] = cls
 
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        table = self._table()
-        if table is None:
-            raise TypeError("build a variant with variants.CViT(name) or variants.variant_class(name)")
+        if self.variant not in CVIT_FAMILY:
+            raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
         if cfg != SUPPORTED:
@@ -63,9 +203,9 @@ class VariantCViT(nn.Module):
             raise ValueError(f"dtype must be one of {list(_lib.DTYPES)}")
         self.dtype_name = dtype
         self.patch_size = patch_size
-        self.table = table
-        for name, shape, kind in self._param_specs(dim=dim, depth=depth, mlp_dim=mlp_dim, num_classes=num_classes,
-                                                   channels=channels, patch_size=patch_size):
+        self.table = CVIT_FAMILY[self.variant]
+        for name, shape, kind in param_specs(self.table, dim=dim, depth=depth, mlp_dim=mlp_dim,
+                                             num_classes=num_classes, channels=channels, patch_size=patch_size):
             *path, leaf = name.split(".")
             mod = self
             for p in path:
@@ -79,15 +219,9 @@ class VariantCViT(nn.Module):
                 mod.register_parameter(leaf, nn.Parameter(t))
         self._prep = None
         self._ctx = None
+        self._smfa_scratch = None          # fac_smfa's scratch, see _scratch_for
+        self._smfa_outgrown = []
         self.eval()
-
-    # what a subclass with another stem replaces (dconv.py): the table, the
-    # state_dict's layout, _prepare_stem and stem_features
-    def _table(self):
-        return VARIANTS.get(self.variant)
-
-    def _param_specs(self, **kw):
-        return variant_param_specs(self.variant, **kw)
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -111,21 +245,30 @@ class VariantCViT(nn.Module):
         except Exception:
             pass
 
-    def folded_layers(self):
-        """(weight, bias, relu, pool) per conv, DEConv and BatchNorm folded in fp32."""
-        sd = self.state_dict()
-        out = []
-        for seq, idx, kind, _ci, _co, bn, relu, pl in self.table["layers"]:
-            p = f"{seq}.{idx}"
+    def _fold(self, sd):
+        """Per table layer its operands in fp32 on the host: (weight, bias) with
+        the DEConv and the BatchNorm folded, or dconv.idw_fold's five."""
+        from .dconv import idw_fold
+        for seq, idx, kind, _ci, _co, bn, _relu, _pool in self.table["layers"]:
+            p, q = f"{seq}.{idx}", f"{seq}.{bn}"
+            if kind == "idw":
+                yield idw_fold(sd, p, q)
+                continue
             w, b = (sd[p + ".weight"], sd[p + ".bias"]) if kind == "conv" else deconv_fold(sd, p)
             if bn is not None:
-                q = f"{seq}.{bn}"
-                w, b = fold_bn(w, b, sd[q + ".weight"], sd[q + ".bias"], sd[q + ".running_mean"],
-                               sd[q + ".running_var"], BN_EPS)
+                yield fold_bn(w, b, sd[q + ".weight"], sd[q + ".bias"], sd[q + ".running_mean"],
+                              sd[q + ".running_var"], BN_EPS)
             else:
-                w, b = fold_bn(w, b, None, None, None, None, BN_EPS)
-            out.append((w, b, relu, pl))
-        return out
+                yield fold_bn(w, b, None, None, None, None, BN_EPS)
+
+    def folded_layers(self):
+        """(weight, bias, relu, pool) per conv; for a table with InceptionDWConv2d
+        layers, ("conv", weight, bias, pool) or ("idw", w_hw, w_w, w_h, scale, shift, pool)."""
+        layers = self.table["layers"]
+        ops = self._fold(self.state_dict())
+        if any(l[2] == "idw" for l in layers):
+            return [("idw" if l[2] == "idw" else "conv", *o, l[7]) for l, o in zip(layers, ops)]
+        return [(*o, l[6], l[7]) for l, o in zip(layers, ops)]
 
     def _prepare(self, device: torch.device):
         idx = device.index if device.index is not None else torch.cuda.current_device()
@@ -133,9 +276,8 @@ class VariantCViT(nn.Module):
         if self._prep == (idx, v):
             return
         sd = self.state_dict()
-        self._prepare_stem(sd, device)
         self._zero = torch.zeros(128, dtype=torch.int16, device=device)   # zero-padding source page
-        self._prepare_ggca(sd, device, self._ggca_after())
+        self._prepare_stem(sd, device)
         self._prepare_tail(sd, idx)
         self._prep = (idx, v)
 
@@ -158,39 +300,37 @@ class VariantCViT(nn.Module):
         return out.view(TORCH16[dt]).to(device)
 
     def _prepare_stem(self, sd, device):
-        """The fused first block's operands (self._stem) and one entry per later conv (self._layers)."""
-        layers, H = [], 224
-        for i, (w, b, relu, pl) in enumerate(self.folded_layers()):
-            co, ci = w.shape[:2]
-            layers.append((self._packed_conv(w, 0 if i == 0 else H, device), b.to(device), H, ci, co, pl, relu))
-            if pl:
-                H //= 2
-        (w1, b1, *_), (w2, b2, *_), (w3, b3, *_) = layers[:3]
-        self._stem = (w1, b1, w2, b2, w3, b3)
-        self._layers = layers[3:]
-
-    def _ggca_after(self):
-        """After how many of self._layers the GGCA combine runs (None: no GGCA)."""
-        if self.table["ggca"] is None:
-            return None
-        site = self.table["ggca"][0]
-        seqs = [l[0] for l in self.table["layers"]]
-        after = len(seqs) if site == "stem" else max(i for i, s in enumerate(seqs) if s == site) + 1
-        return after - 3
-
-    def _prepare_ggca(self, sd, device, after):
-        """self._ggca: the site (index into self._layers), its shape, op and device weights."""
-        self._ggca = None
-        if self.table["ggca"] is not None:
-            _site, chw, op = self.table["ggca"]
-            g = "ggca.shared_conv."
-            f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
-            cr, cg = sd[g + "0.weight"].shape[:2]
-            self._ggca = (after, chw, self.ggca_ops[op],
-                          (f32(sd[g + "0.weight"].reshape(cr, cg)), f32(sd[g + "0.bias"]),
-                           f32(torch.stack([sd[g + "1.running_mean"], sd[g + "1.running_var"], sd[g + "1.weight"],
-                                            sd[g + "1.bias"]])),
-                           f32(sd[g + "3.weight"].reshape(cg, cr)), f32(sd[g + "3.bias"])))
+        """self._steps: per stem_plan step (step, the class's _step_<kind> function,
+        its device operands); self._ggca / self._smfa: those steps' operands or None."""
+        from .other import smfa16, smfa_fold, smfa_pack
+        self._smfa16 = smfa16          # bound here: other.py imports this module
+        folded = list(self._fold(sd))
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        self._ggca = self._smfa = None
+        self._steps = []
+        for s in stem_plan(self.table):
+            if s.kind == "stem224":
+                ops = tuple(t for i, (w, b) in enumerate(folded[:3])
+                            for t in (self._packed_conv(w, 0 if i == 0 else 224, device), b.to(device)))
+            elif s.kind == "conv":
+                w, b = folded[s.labels[0] - 1]
+                if w.shape[1] < s.ci:      # 3 -> 32 on the 32-channel packed input
+                    w = torch.cat([w, torch.zeros(w.shape[0], s.ci - w.shape[1], 3, 3)], 1)
+                ops = (self._packed_conv(w, s.H, device), b.to(device))
+            elif s.kind == "idw":
+                ops = tuple(t.to(device) for t in folded[s.labels[0] - 1])
+            elif s.kind == "smfa":
+                ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
+            elif s.kind == "ggca":
+                g = "ggca.shared_conv."
+                cr, cg = sd[g + "0.weight"].shape[:2]
+                ops = self._ggca = (f32(sd[g + "0.weight"].reshape(cr, cg)), f32(sd[g + "0.bias"]),
+                                    f32(torch.stack([sd[g + "1.running_mean"], sd[g + "1.running_var"],
+                                                     sd[g + "1.weight"], sd[g + "1.bias"]])),
+                                    f32(sd[g + "3.weight"].reshape(cg, cr)), f32(sd[g + "3.bias"]))
+            else:
+                ops = ()
+            self._steps.append((s, getattr(type(self), "_step_" + s.kind), ops))
 
     def _prepare_tail(self, sd, idx):
         """The CViT tail (embedding .. head) on a context without a conv stem."""
@@ -224,55 +364,104 @@ class VariantCViT(nn.Module):
         arr = (_lib.TensorDesc * len(descs))(*descs)
         _lib.check(lib.fac_load_weights(h, ctypes.cast(arr, ctypes.c_void_p), len(descs)), h, "fac_load_weights")
 
+    def _scratch_for(self, B: int, s: Step, device) -> torch.Tensor:
+        """fac_smfa's scratch for B crops: one buffer per model, grown when a
+        larger batch comes and otherwise reused, so that after reserve(max_batch)
+        a forward of up to max_batch crops allocates none.  A buffer that was
+        outgrown is kept: a graph captured with it still points at it."""
+        need = _lib.load().fac_smfa_scratch_bytes(B, s.H, s.H, s.co)
+        buf = self._smfa_scratch
+        if buf is None or buf.numel() < need or buf.device != torch.device(device):
+            if buf is not None:
+                self._smfa_outgrown.append(buf)
+            self._smfa_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
+        return buf
+
     def reserve(self, max_batch: int, device=None):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._prepare(dev)
         _lib.check(_lib.load().fac_reserve(self._ctx, int(max_batch)), self._ctx, "fac_reserve")
+        for s, _run, ops in self._steps:
+            if s.kind == "smfa":
+                self._scratch_for(int(max_batch), s, ops.device)
 
-    # ------------------------------------------------------------------ forward
+    # ------------------------------------------------------------------ the stem's launches
+    # _step_<kind>(x, s, ops, u8, st) -> the step's output, a new tensor; x: the
+    # map before it, for the first step the forward's input; st: the current stream
+    def _step_stem224(self, src, s, ops, u8, st):
+        x = torch.empty(src.shape[0], 112, 112, 32, dtype=TORCH16[self.dtype_name], device=src.device)
+        _lib.check(_lib.load().fac_stem224(_lib.DTYPES[self.dtype_name], int(u8), src.data_ptr(),
+                                           *[t.data_ptr() for t in ops], x.data_ptr(), src.shape[0], st), None,
+                   "fac_stem224")
+        return x
+
+    def _step_pack32(self, src, s, ops, u8, st):
+        norm = dict(div=255.0, mean=MEAN, std=STD) if u8 else {}
+        x = pack_input(src, dtype=self.dtype_name, u8=u8, spatial=(s.H, s.H), c_pad=s.co, **norm)
+        return x.view(src.shape[0], s.H, s.H, s.co)
+
+    def _conv3x3(self, x, s, ops, pool, relu, y, st):
+        wpk, b = ops
+        _lib.check(_lib.load().fac_conv3x3(_lib.DTYPES[self.dtype_name], x.data_ptr(), wpk.data_ptr(), b.data_ptr(),
+                                           y.data_ptr(), x.shape[0], s.H, s.ci, s.co, pool, relu,
+                                           self._zero.data_ptr(), st), None, "fac_conv3x3")
+        return y
+
+    def _step_conv(self, x, s, ops, u8, st):
+        Ho = s.H // 2 if s.pool else s.H
+        y = torch.empty(x.shape[0], Ho, Ho, s.co, dtype=TORCH16[self.dtype_name], device=x.device)
+        return self._conv3x3(x, s, ops, int(s.pool), int(s.relu), y, st)
+
+    def _step_idw(self, x, s, ops, u8, st):
+        Ho = s.H // 2 if s.pool else s.H
+        y = torch.empty(x.shape[0], Ho, Ho, s.co, dtype=TORCH16[self.dtype_name], device=x.device)
+        _lib.check(_lib.load().fac_idwconv(_lib.DTYPES[self.dtype_name], x.data_ptr(), y.data_ptr(), x.shape[0], s.H,
+                                           s.H, s.co, *[t.data_ptr() for t in ops], int(s.pool), st), None,
+                   "fac_idwconv")
+        return y
+
+    def _step_smfa(self, x, s, ops, u8, st):
+        return self._smfa16(x, ops, self.dtype_name, residual=True,
+                            scratch=self._scratch_for(x.shape[0], s, x.device))
+
+    def _step_ggca(self, x, s, ops, u8, st):
+        return self.ggca_combine16(x)
+
     def ggca_combine16(self, f: torch.Tensor) -> torch.Tensor:
-        """x * GGCA(x) or x + GGCA(x), the variant's, on [B,H,W,C] 16-bit NHWC."""
-        _after, (C, H, W), op, (w1, b1, bn4, w2, b2) = self._ggca
+        """The class's GGCA step on [B,H,W,C] 16-bit NHWC: x * GGCA(x), x + GGCA(x) or GGCA(x)."""
+        _site, (C, H, W), op = self.table["ggca"]
         if tuple(f.shape[1:]) != (H, W, C):
             raise ValueError(f"expected features [B,{H},{W},{C}], got {tuple(f.shape)}")
         out = torch.empty_like(f)
-        _lib.check(_lib.load().fac_ggca_apply(_lib.DTYPES[self.dtype_name], f.data_ptr(), f.shape[0], H, W, C,
-                                              GGCA_GROUPS, w1.data_ptr(), b1.data_ptr(), bn4.data_ptr(),
-                                              w2.data_ptr(), b2.data_ptr(), op, out.data_ptr(),
-                                              torch.cuda.current_stream(f.device).cuda_stream), None, "fac_ggca_apply")
+        lib = _lib.load()
+        st = torch.cuda.current_stream(f.device).cuda_stream
+        head = (_lib.DTYPES[self.dtype_name], f.data_ptr(), f.shape[0], H, W, C, GGCA_GROUPS,
+                *[t.data_ptr() for t in self._ggca])
+        if GGCA_OPS[op] == GGCA_ATT:
+            _lib.check(lib.fac_ggca_scale(*head, out.data_ptr(), st), None, "fac_ggca_scale")
+        else:
+            _lib.check(lib.fac_ggca_apply(*head, GGCA_OPS[op], out.data_ptr(), st), None, "fac_ggca_apply")
         return out
 
-    def stem_features(self, src: torch.Tensor, u8: bool, upto=None) -> torch.Tensor:
-        """The conv stem with the GGCA combine at its site -> [B,7,7,512] 16-bit
-        NHWC.  src: uint8 NHWC crops (u8) or normalised fp32 NCHW images.
-        upto="ggca": stop right after the combine (RepBn3: the [B,56,56,64] map)."""
-        lib = _lib.load()
-        dti = _lib.DTYPES[self.dtype_name]
-        B, dev = src.shape[0], src.device
-        st = torch.cuda.current_stream(dev).cuda_stream
-        x = torch.empty(B, 112, 112, 32, dtype=TORCH16[self.dtype_name], device=dev)
-        w1, b1, w2, b2, w3, b3 = self._stem
-        _lib.check(lib.fac_stem224(dti, int(u8), src.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                   b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), x.data_ptr(), B, st), None,
-                   "fac_stem224")
-        site = self._ggca[0] if self._ggca is not None else None
-        for i, (wpk, b, H, ci, co, pl, relu) in enumerate(self._layers):
-            Ho = H // 2 if pl else H
-            y = torch.empty(B, Ho, Ho, co, dtype=x.dtype, device=dev)
-            _lib.check(lib.fac_conv3x3(dti, x.data_ptr(), wpk.data_ptr(), b.data_ptr(), y.data_ptr(), B, H, ci, co,
-                                       int(pl), int(relu), self._zero.data_ptr(), st), None, "fac_conv3x3")
-            x = y
-            if site == i + 1:
-                x = self.ggca_combine16(x)
-                if upto == "ggca":
-                    return x
+    # ------------------------------------------------------------------ forward
+    def _walk(self, x, u8: bool, steps):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        for s, run, ops in steps:
+            x = run(self, x, s, ops, u8, st)
         return x
+
+    def stem_features(self, src: torch.Tensor, u8: bool, upto=None) -> torch.Tensor:
+        """The conv stem with the class's blocks at their sites -> [B,7,7,512]
+        16-bit NHWC.  src: uint8 NHWC crops (u8) or normalised fp32 NCHW images.
+        upto stops early and returns that map (steps_upto)."""
+        steps = self._steps
+        return self._walk(src, u8, steps[:steps_upto([s for s, _run, _ops in steps], upto)])
 
     def _run(self, src: torch.Tensor, u8: bool, pos_index, want_probs: bool):
         B = src.shape[0]
         dev = src.device
         pidx = _pos_index(B, pos_index, dev)
-        f = self.stem_features(src, u8)
+        f = self._walk(src, u8, self._steps)
         logits = torch.empty(B, SUPPORTED["num_classes"], dtype=torch.float32, device=dev)
         probs = torch.empty_like(logits) if want_probs else None
         _lib.check(_lib.load().fac_forward_features(self._ctx, f.data_ptr(), B, pidx.data_ptr(), None,
@@ -304,23 +493,30 @@ class VariantCViT(nn.Module):
         return (logits, probs) if return_probs else logits
 
 
-_CLASSES: dict = {}
+_CLASSES: dict = {}      # variant name -> class, filled by VariantCViT.__init_subclass__
+_MODULES = {REPBN8_NAME: "repbn8"}   # classes with methods of their own live in a module of theirs
 
 
 def variant_class(name: str) -> type:
-    """The drop-in class of reference file ``model/<name>.py`` (its ``CViT``)."""
-    if name not in VARIANTS:
-        raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(VARIANT_NAMES)}")
+    """The drop-in class of reference file ``model/<name>.py`` or ``model/other/<name>.py`` (its ``CViT``)."""
+    if name not in CVIT_FAMILY:
+        raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES)}")
     if name not in _CLASSES:
-        _CLASSES[name] = type("CViT", (VariantCViT,), {"variant": name, "__module__": __name__,
-                                                       "__qualname__": f"CViT[{name}]",
-                                                       "__doc__": f"{name}.CViT on gfx950 (inference)."})
+        if name in _MODULES:
+            importlib.import_module(f"{__package__}.{_MODULES[name]}")
+        else:
+            type("CViT", (VariantCViT,), {"variant": name, "__module__": __name__, "__qualname__": f"CViT[{name}]",
+                                          "__doc__": f"{name}.CViT on gfx950 (inference)."})
     return _CLASSES[name]
 
 
 def CViT(name: str, *args, **kwargs) -> VariantCViT:
-    """``variant_class(name)(*args, **kwargs)``: the reference's constructor arguments plus ``dtype``."""
+    """One of the eight ``VARIANTS``: ``variant_class(name)(*args, **kwargs)``, the reference's constructor
+    arguments plus ``dtype``."""
+    if name not in VARIANTS:
+        raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(VARIANT_NAMES)}")
     return variant_class(name)(*args, **kwargs)
 
 
-__all__ = ["CViT", "VARIANTS", "VARIANT_NAMES", "VariantCViT", "variant_class"]
+__all__ = ["CViT", "VARIANTS", "VARIANT_NAMES", "VariantCViT", "deconv_fold", "stem_plan", "steps_upto",
+           "variant_class"]

@@ -861,72 +861,11 @@ def _deconv_specs(p, c):
     return out
 
 
-def repbn8_param_specs(dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """(name, shape, kind) for every key of the RepBn8 CViT's state_dict, in its order."""
-    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
-    for seq, idx, kind, ci, co, bn, _relu, _pool in REPBN8_LAYERS:
-        p = f"{seq}.{idx}"
-        if kind == "conv":
-            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
-        else:
-            specs += _deconv_specs(p, co)
-        if bn is not None:
-            specs += _bn_specs(f"{seq}.{bn}", co)
-    pdim = channels * patch_size ** 2
-    specs += [("patch_to_embedding.weight", (dim, pdim), "lin"), ("patch_to_embedding.bias", (dim,), "lbias")]
-    for l in range(depth):
-        p = f"transformer.layers.{l}"
-        specs += [(f"{p}.0.fn.norm.weight", (dim,), "gamma"), (f"{p}.0.fn.norm.bias", (dim,), "beta"),
-                  (f"{p}.0.fn.fn.to_qkv.weight", (3 * dim, dim), "lin"),
-                  (f"{p}.0.fn.fn.to_out.weight", (dim, dim), "lin"), (f"{p}.0.fn.fn.to_out.bias", (dim,), "lbias"),
-                  (f"{p}.1.fn.norm.warm", (), "warm"), (f"{p}.1.fn.norm.iter", (), "step"),
-                  (f"{p}.1.fn.norm.total_step", (), "step"),
-                  (f"{p}.1.fn.norm.norm1.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.norm1.bias", (dim,), "beta"),
-                  (f"{p}.1.fn.norm.norm2.alpha", (1,), "alpha")]
-        specs += _bn_specs(f"{p}.1.fn.norm.norm2.bn", dim)
-        specs += [(f"{p}.1.fn.fn.net.0.weight", (mlp_dim, dim), "lin"), (f"{p}.1.fn.fn.net.0.bias", (mlp_dim,), "lbias"),
-                  (f"{p}.1.fn.fn.net.2.weight", (dim, mlp_dim), "lin"), (f"{p}.1.fn.fn.net.2.bias", (dim,), "lbias")]
-    specs += [("mlp_head.0.weight", (mlp_dim, dim), "lin"), ("mlp_head.0.bias", (mlp_dim,), "lbias"),
-              ("mlp_head.2.weight", (num_classes, mlp_dim), "head"), ("mlp_head.2.bias", (num_classes,), "lbias")]
-    gc = channels // 4                      # GGCA(512, 7, 7): 4 groups, reduction 16 (:144-172)
-    specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"), ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
-    specs += _bn_specs("ggca.shared_conv.1", gc // 16)
-    specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"), ("ggca.shared_conv.3.bias", (gc,), "cbias")]
-    specs += _deconv_specs("Deconv", 256)   # self.Deconv = DEConv(256) (:454): in the state_dict, never called
-    return specs
-
-
-def make_repbn8_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic RepBn8 weights (same generator).  The five DEConv kernels are
-    drawn at 1/2.8 of the He bound each: their folded sum (with the central-
-    and angular-difference terms) then has about unit gain, so the features
-    stay O(1) through 14 DEConvs (mean |features2| 0.88); LinearNorm's counters are the reference's defaults
-    (warm 0, iter = total_step = 300000) and RepBN (unused at eval) is a
-    plain alpha = 1 / unit BatchNorm."""
-    sd = OrderedDict()
-    for name, shape, kind in repbn8_param_specs(**kw):
-        if kind == "nbt" or kind == "warm":
-            sd[name] = np.array(0, dtype=np.int64)
-        elif kind == "step":
-            sd[name] = np.array(300000, dtype=np.int64)
-        elif kind == "alpha":
-            sd[name] = np.ones(shape, dtype=np.float32)
-        elif kind in ("conv", "dconv"):
-            fan_in = int(np.prod(shape[1:]))
-            a = float(np.sqrt(6.0 / fan_in))
-            if kind == "dconv":
-                a /= 2.8
-            sd[name] = _u(name, shape, seed, -a, a)
-        else:
-            sd[name] = _synthetic(name, shape, kind, seed)
-    return sd
-
-
 # ---------------------------------------------------------------- CViT variants
 # The eight other top-level CViT-main/model/cvit_*.py classes that recombine
-# the parts above (fac_fake_amd/variants.py runs them): the VGG stem as one,
-# two or three nn.Sequentials with plain convs or DEConvs, a GGCA site with
-# x * GGCA(x) or x + GGCA(x), and a LayerNorm or LinearNorm FeedForward PreNorm.
+# the parts above: the VGG stem as one, two or three nn.Sequentials with plain
+# convs or DEConvs, a GGCA site with x * GGCA(x) or x + GGCA(x), and a LayerNorm
+# or LinearNorm FeedForward PreNorm.
 _VARIANT_BLOCKS = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 256, 4), (256, 512, 4)]   # (cin, cout, convs), pool after
 
 
@@ -965,100 +904,28 @@ def _variant_layers(split, kinds: str, bare26: bool = False):
 _REPBN8_KINDS = "cdd cdd cdcd cddd cddd"
 _PLAIN_KINDS = "ccc ccc ccc cccc cccc"
 _MIXED_KINDS = "ccd cdc cdc cddc cccc"
-# name (the reference file's) -> layers; ggca: None or (site, (C, H, W), op) with
-# site "stem" (after the last sequential) or the sequential it follows and op
-# "mul" (x * GGCA(x)) or "add" (x + GGCA(x)); ff_norm: the FeedForward PreNorm,
-# "layernorm" (eps 1e-5) or "linearnorm" (eval: LayerNorm eps 1e-6, plus its
-# counters and unused RepBN branch in the state_dict); deconv: the unused
-# top-level self.Deconv = DEConv(256) exists.
+
+
+# One entry per class, every table's format (see CVIT_FAMILY below).
+def _entry(layers, ggca, ff_norm, deconv, smfa=None):
+    return dict(layers=layers, ggca=ggca, ff_norm=ff_norm, deconv=deconv, smfa=smfa)
+
+
+_STEM_MUL, _STEM_ADD = ("stem", (512, 7, 7), "mul"), ("stem", (512, 7, 7), "add")
 VARIANTS = {
-    "cvit_DEConv": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True), ggca=None, ff_norm="linearnorm",
-                        deconv=True),
-    "cvit_GGCA_ADD": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "mul"),
-                          ff_norm="layernorm", deconv=False),
-    "cvit_GGCA_ADD_DEConv": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True),
-                                 ggca=("stem", (512, 7, 7), "mul"), ff_norm="layernorm", deconv=True),
-    "cvit_GGCA_ADD_RepBn": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "add"),
-                                ff_norm="linearnorm", deconv=False),
-    "cvit_GGCA_ADD_DEConv_RepBn": dict(layers=_variant_layers((4, 1), _MIXED_KINDS),
-                                       ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
-    "cvit_GGCA_ADD_DEConv_RepBn3": dict(layers=_variant_layers((2, 2, 1), _MIXED_KINDS),
-                                        ggca=("features1", (64, 56, 56), "add"), ff_norm="linearnorm", deconv=True),
-    "cvit_GGCA_ADD_DEConv_RepBn4": dict(layers=_variant_layers((4, 1), "cdd cdd cdcd cddc ccdc", True),
-                                        ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
-    "cvit_GGCA_ADD_DEConv_RepBn5": dict(layers=_variant_layers((4, 1), _REPBN8_KINDS, True),
-                                        ggca=("stem", (512, 7, 7), "add"), ff_norm="linearnorm", deconv=True),
+    "cvit_DEConv": _entry(_variant_layers((4, 1), _REPBN8_KINDS, True), None, "linearnorm", True),
+    "cvit_GGCA_ADD": _entry(_variant_layers((5,), _PLAIN_KINDS), _STEM_MUL, "layernorm", False),
+    "cvit_GGCA_ADD_DEConv": _entry(_variant_layers((4, 1), _REPBN8_KINDS, True), _STEM_MUL, "layernorm", True),
+    "cvit_GGCA_ADD_RepBn": _entry(_variant_layers((5,), _PLAIN_KINDS), _STEM_ADD, "linearnorm", False),
+    "cvit_GGCA_ADD_DEConv_RepBn": _entry(_variant_layers((4, 1), _MIXED_KINDS), _STEM_ADD, "linearnorm", True),
+    "cvit_GGCA_ADD_DEConv_RepBn3": _entry(_variant_layers((2, 2, 1), _MIXED_KINDS),
+                                          ("features1", (64, 56, 56), "add"), "linearnorm", True),
+    "cvit_GGCA_ADD_DEConv_RepBn4": _entry(_variant_layers((4, 1), "cdd cdd cdcd cddc ccdc", True), _STEM_ADD,
+                                          "linearnorm", True),
+    "cvit_GGCA_ADD_DEConv_RepBn5": _entry(_variant_layers((4, 1), _REPBN8_KINDS, True), _STEM_ADD, "linearnorm",
+                                          True),
 }
 VARIANT_NAMES = tuple(VARIANTS)
-
-
-def variant_param_specs(name: str, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """(name, shape, kind) for every key of variant `name`'s state_dict, in the reference's order."""
-    return _table_param_specs(VARIANTS[name], dim, depth, mlp_dim, num_classes, channels, patch_size)
-
-
-def _table_param_specs(v, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """variant_param_specs for one table entry (VARIANTS' or OTHER_VARIANTS')."""
-    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
-    for seq, idx, kind, ci, co, bn, _relu, _pool in v["layers"]:
-        p = f"{seq}.{idx}"
-        if kind == "conv":
-            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
-        else:
-            specs += _deconv_specs(p, co)
-        if bn is not None:
-            specs += _bn_specs(f"{seq}.{bn}", co)
-    pdim = channels * patch_size ** 2
-    specs += [("patch_to_embedding.weight", (dim, pdim), "lin"), ("patch_to_embedding.bias", (dim,), "lbias")]
-    for l in range(depth):
-        p = f"transformer.layers.{l}"
-        specs += [(f"{p}.0.fn.norm.weight", (dim,), "gamma"), (f"{p}.0.fn.norm.bias", (dim,), "beta"),
-                  (f"{p}.0.fn.fn.to_qkv.weight", (3 * dim, dim), "lin"),
-                  (f"{p}.0.fn.fn.to_out.weight", (dim, dim), "lin"), (f"{p}.0.fn.fn.to_out.bias", (dim,), "lbias")]
-        if v["ff_norm"] == "linearnorm":
-            specs += [(f"{p}.1.fn.norm.warm", (), "warm"), (f"{p}.1.fn.norm.iter", (), "step"),
-                      (f"{p}.1.fn.norm.total_step", (), "step"),
-                      (f"{p}.1.fn.norm.norm1.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.norm1.bias", (dim,), "beta"),
-                      (f"{p}.1.fn.norm.norm2.alpha", (1,), "alpha")]
-            specs += _bn_specs(f"{p}.1.fn.norm.norm2.bn", dim)
-        else:
-            specs += [(f"{p}.1.fn.norm.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.bias", (dim,), "beta")]
-        specs += [(f"{p}.1.fn.fn.net.0.weight", (mlp_dim, dim), "lin"), (f"{p}.1.fn.fn.net.0.bias", (mlp_dim,), "lbias"),
-                  (f"{p}.1.fn.fn.net.2.weight", (dim, mlp_dim), "lin"), (f"{p}.1.fn.fn.net.2.bias", (dim,), "lbias")]
-    specs += [("mlp_head.0.weight", (mlp_dim, dim), "lin"), ("mlp_head.0.bias", (mlp_dim,), "lbias"),
-              ("mlp_head.2.weight", (num_classes, mlp_dim), "head"), ("mlp_head.2.bias", (num_classes,), "lbias")]
-    if v["ggca"] is not None:
-        gc = v["ggca"][1][0] // 4               # GGCA(C, H, W): 4 groups, reduction 16
-        specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"),
-                  ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
-        specs += _bn_specs("ggca.shared_conv.1", gc // 16)
-        specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"),
-                  ("ggca.shared_conv.3.bias", (gc,), "cbias")]
-    if v["deconv"]:
-        specs += _deconv_specs("Deconv", 256)   # in the state_dict, never called
-    return specs
-
-
-def make_variant_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic weights of variant `name`: make_repbn8_state_dict's generator
-    (a key that RepBn8 also has gets the same values for the same seed)."""
-    sd = OrderedDict()
-    for key, shape, kind in variant_param_specs(name, **kw):
-        if kind == "nbt" or kind == "warm":
-            sd[key] = np.array(0, dtype=np.int64)
-        elif kind == "step":
-            sd[key] = np.array(300000, dtype=np.int64)
-        elif kind == "alpha":
-            sd[key] = np.ones(shape, dtype=np.float32)
-        elif kind in ("conv", "dconv"):
-            fan_in = int(np.prod(shape[1:]))
-            a = float(np.sqrt(6.0 / fan_in))
-            if kind == "dconv":
-                a /= 2.8
-            sd[key] = _u(key, shape, seed, -a, a)
-        else:
-            sd[key] = _synthetic(key, shape, kind, seed)
-    return sd
 
 
 # ---------------------------------------------------------------- CViT GGCA_ADD_DConv
@@ -1087,59 +954,19 @@ def _idw_specs(p, c):
             (f"{p}.dwconv_h.weight", (gc, 1, IDW_BAND, 1), "dw"), (f"{p}.dwconv_h.bias", (gc,), "cbias")]
 
 
-def dconv_param_specs(dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """(name, shape, kind) for every key of cvit_GGCA_ADD_DConv.CViT's state_dict, in its order (238 keys)."""
-    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
-    for idx, kind, ci, co, bn, _pool in DCONV_LAYERS:
-        p = f"features.{idx}"
-        if kind == "conv":
-            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
-        else:
-            specs += _idw_specs(p, co)
-        specs += _bn_specs(f"features.{bn}", co)
-    specs += [s for s in cvit_param_specs(dim, depth, mlp_dim, num_classes, channels, patch_size)
-              if not s[0].startswith("features.") and s[0] not in ("pos_embedding", "cls_token")]
-    gc = 512 // 4                           # GGCA(512, 7, 7): 4 groups, reduction 16
-    specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"), ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
-    specs += _bn_specs("ggca.shared_conv.1", gc // 16)
-    specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"), ("ggca.shared_conv.3.bias", (gc,), "cbias")]
-    return specs
-
-
-def make_dconv_state_dict(seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic cvit_GGCA_ADD_DConv weights (same generator; a key the base
-    CViT or a variant also has gets the same values for the same seed)."""
-    sd = OrderedDict()
-    for key, shape, kind in dconv_param_specs(**kw):
-        if kind == "nbt":
-            sd[key] = np.array(0, dtype=np.int64)
-        elif kind == "conv":
-            a = float(np.sqrt(6.0 / int(np.prod(shape[1:]))))
-            sd[key] = _u(key, shape, seed, -a, a)
-        elif kind == "dw":
-            a = float(DCONV_DW_GAIN * np.sqrt(3.0 / int(np.prod(shape[1:]))))
-            sd[key] = _u(key, shape, seed, -0.5 * a, 1.5 * a)
-        else:
-            sd[key] = _synthetic(key, shape, kind, seed)
-    return sd
-
-
 # ---------------------------------------------------------------- CViT model/other/
 # Four classes of CViT-main/model/other/ that keep the CViT's channel / pool
-# plan, patch and tail (fac_fake_amd/other.py runs them).  The entries have
-# VARIANTS' format (plain convs, LayerNorm in both PreNorms) plus `smfa`: None,
-# or the sequential that x + SMFA(x) follows, and a third GGCA op, "att": x = GGCA(x), the module's own
-# output x * att_h * att_w (VARIANTS' "mul" is x * GGCA(x)).  cvit_GGCA_SMFA has GGCA on the
+# plan, patch and tail: plain convs, LayerNorm in both PreNorms, GGCA as the
+# module's own output ("att") or added, and in cvit_GGCA_SMFA both GGCA on the
 # stem output AND the SMFA block (:160-203) on the 256x14x14 map.
 OTHER_VARIANTS = {
-    "cvit_GGCA": dict(layers=_variant_layers((5,), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "att"),
-                      ff_norm="layernorm", deconv=False, smfa=None),
-    "cvit_GGCA4": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("features1", (256, 14, 14), "att"),
-                       ff_norm="layernorm", deconv=False, smfa=None),
-    "cvit_GGCA_ADD3": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("features1", (256, 14, 14), "add"),
-                           ff_norm="layernorm", deconv=False, smfa=None),
-    "cvit_GGCA_SMFA": dict(layers=_variant_layers((4, 1), _PLAIN_KINDS), ggca=("stem", (512, 7, 7), "add"),
-                           ff_norm="layernorm", deconv=False, smfa="features1"),
+    "cvit_GGCA": _entry(_variant_layers((5,), _PLAIN_KINDS), ("stem", (512, 7, 7), "att"), "layernorm", False),
+    "cvit_GGCA4": _entry(_variant_layers((4, 1), _PLAIN_KINDS), ("features1", (256, 14, 14), "att"), "layernorm",
+                         False),
+    "cvit_GGCA_ADD3": _entry(_variant_layers((4, 1), _PLAIN_KINDS), ("features1", (256, 14, 14), "add"),
+                             "layernorm", False),
+    "cvit_GGCA_SMFA": _entry(_variant_layers((4, 1), _PLAIN_KINDS), _STEM_ADD, "layernorm", False,
+                             smfa="features1"),
 }
 OTHER_NAMES = tuple(OTHER_VARIANTS)
 SMFA_DIM = 256
@@ -1166,15 +993,6 @@ def _smfa_specs(p, c):
     return specs
 
 
-def other_param_specs(name: str, **kw):
-    """(name, shape, kind) for every key of model/other/<name>.py's CViT, in its order (202; SMFA: 218)."""
-    v = OTHER_VARIANTS[name]
-    specs = _table_param_specs(v, **kw)
-    if v["smfa"] is not None:
-        specs += _smfa_specs("smfa", SMFA_DIM)
-    return specs
-
-
 def _signed(name, shape, seed, lo, hi):
     """Magnitudes in [lo, hi) with a random sign."""
     u = uniform(name, int(np.prod(shape)), seed)
@@ -1182,17 +1000,101 @@ def _signed(name, shape, seed, lo, hi):
     return (np.where(u < 0, -mag, mag)).astype(np.float32).reshape(shape)
 
 
-def make_other_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic weights of model/other/<name>.py (make_variant_state_dict's
-    generator: a key another CViT also has gets the same values for the same
-    seed; the SMFA block's scheme is described at SMFA_GAINS)."""
+# ---------------------------------------------------------------- the CViT variant family
+# The fourteen classes above share the CViT's channel / pool plan, its single
+# 7x7 patch, tail and pos_embedding rule (fac_fake_amd/variants.py runs them all
+# from these entries).  name (the reference file's) -> dict(
+#   layers   one REPBN8_LAYERS 8-tuple per stem layer, kind "conv" | "deconv"
+#            (DEConv) | "idw" (InceptionDWConv2d);
+#   ggca     None or (site, (C, H, W), op): site "stem" (after the last
+#            sequential) or the sequential it follows; op "mul" x * GGCA(x), "add"
+#            x + GGCA(x), "att" x = GGCA(x), the module's own x * att_h * att_w;
+#   ff_norm  the FeedForward PreNorm, "layernorm" (eps 1e-5) or "linearnorm"
+#            (eval: LayerNorm eps 1e-6, plus its counters and unused RepBN branch
+#            in the state_dict);
+#   deconv   the unused top-level self.Deconv = DEConv(256) exists;
+#   smfa     None or the sequential that x + SMFA(x) follows).
+REPBN8_NAME, DCONV_NAME = "cvit_GGCA_ADD_DEConv_RepBn8", "cvit_GGCA_ADD_DConv"
+CVIT_FAMILY = {
+    REPBN8_NAME: _entry(REPBN8_LAYERS, _STEM_MUL, "linearnorm", True),
+    **VARIANTS,
+    DCONV_NAME: _entry([("features", idx, kind, ci, co, bn, True, pool) for idx, kind, ci, co, bn, pool in DCONV_LAYERS],
+                       _STEM_ADD, "layernorm", False),
+    **OTHER_VARIANTS,
+}
+FAMILY_NAMES = tuple(CVIT_FAMILY)
+
+
+def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
+    """(name, shape, kind) for every key of one CVIT_FAMILY entry's state_dict, in the reference's order."""
+    specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
+    for seq, idx, kind, ci, co, bn, _relu, _pool in entry["layers"]:
+        p = f"{seq}.{idx}"
+        if kind == "conv":
+            specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
+        else:
+            specs += _deconv_specs(p, co) if kind == "deconv" else _idw_specs(p, co)
+        if bn is not None:
+            specs += _bn_specs(f"{seq}.{bn}", co)
+    pdim = channels * patch_size ** 2
+    specs += [("patch_to_embedding.weight", (dim, pdim), "lin"), ("patch_to_embedding.bias", (dim,), "lbias")]
+    for l in range(depth):
+        p = f"transformer.layers.{l}"
+        specs += [(f"{p}.0.fn.norm.weight", (dim,), "gamma"), (f"{p}.0.fn.norm.bias", (dim,), "beta"),
+                  (f"{p}.0.fn.fn.to_qkv.weight", (3 * dim, dim), "lin"),
+                  (f"{p}.0.fn.fn.to_out.weight", (dim, dim), "lin"), (f"{p}.0.fn.fn.to_out.bias", (dim,), "lbias")]
+        if entry["ff_norm"] == "linearnorm":
+            specs += [(f"{p}.1.fn.norm.warm", (), "warm"), (f"{p}.1.fn.norm.iter", (), "step"),
+                      (f"{p}.1.fn.norm.total_step", (), "step"),
+                      (f"{p}.1.fn.norm.norm1.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.norm1.bias", (dim,), "beta"),
+                      (f"{p}.1.fn.norm.norm2.alpha", (1,), "alpha")]
+            specs += _bn_specs(f"{p}.1.fn.norm.norm2.bn", dim)
+        else:
+            specs += [(f"{p}.1.fn.norm.weight", (dim,), "gamma"), (f"{p}.1.fn.norm.bias", (dim,), "beta")]
+        specs += [(f"{p}.1.fn.fn.net.0.weight", (mlp_dim, dim), "lin"), (f"{p}.1.fn.fn.net.0.bias", (mlp_dim,), "lbias"),
+                  (f"{p}.1.fn.fn.net.2.weight", (dim, mlp_dim), "lin"), (f"{p}.1.fn.fn.net.2.bias", (dim,), "lbias")]
+    specs += [("mlp_head.0.weight", (mlp_dim, dim), "lin"), ("mlp_head.0.bias", (mlp_dim,), "lbias"),
+              ("mlp_head.2.weight", (num_classes, mlp_dim), "head"), ("mlp_head.2.bias", (num_classes,), "lbias")]
+    if entry["ggca"] is not None:
+        gc = entry["ggca"][1][0] // 4           # GGCA(C, H, W): 4 groups, reduction 16
+        specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"),
+                  ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
+        specs += _bn_specs("ggca.shared_conv.1", gc // 16)
+        specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"),
+                  ("ggca.shared_conv.3.bias", (gc,), "cbias")]
+    if entry["deconv"]:
+        specs += _deconv_specs("Deconv", 256)   # self.Deconv = DEConv(256): in the state_dict, never called
+    if entry["smfa"] is not None:
+        specs += _smfa_specs("smfa", SMFA_DIM)
+    return specs
+
+
+def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for (name, shape, kind) specs of the family (make_state_dict's
+    generator: a key two classes share gets the same values for the same seed).
+    The five DEConv kernels ("dconv") are drawn at 1/2.8 of the He bound each:
+    their folded sum (with the central- and angular-difference terms) then has
+    about unit gain, so the features stay O(1) through 14 DEConvs (RepBn8: mean
+    |features2| 0.88).  LinearNorm's counters are the reference's defaults (warm
+    0, iter = total_step = 300000) and its RepBN (unused at eval) a plain alpha =
+    1 / unit BatchNorm.  The InceptionDWConv2d taps ("dw") are described at
+    DCONV_DW_GAIN, the SMFA block's scheme at SMFA_GAINS."""
     sd = OrderedDict()
-    for key, shape, kind in other_param_specs(name, **kw):
-        if kind == "nbt":
+    for key, shape, kind in specs:
+        if kind in ("nbt", "warm"):
             sd[key] = np.array(0, dtype=np.int64)
-        elif kind == "conv":
+        elif kind == "step":
+            sd[key] = np.array(300000, dtype=np.int64)
+        elif kind == "alpha":
+            sd[key] = np.ones(shape, dtype=np.float32)
+        elif kind in ("conv", "dconv"):
             a = float(np.sqrt(6.0 / int(np.prod(shape[1:]))))
+            if kind == "dconv":
+                a /= 2.8
             sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "dw":
+            a = float(DCONV_DW_GAIN * np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -0.5 * a, 1.5 * a)
         elif kind == "smfa_pw":
             gain = SMFA_GAINS[key[len("smfa."):-len(".weight")]]
             a = float(gain * np.sqrt(3.0 / shape[1]))
@@ -1210,3 +1112,41 @@ def make_other_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, n
         else:
             sd[key] = _synthetic(key, shape, kind, seed)
     return sd
+
+
+def make_family_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights of the class of reference file `name` (any of FAMILY_NAMES)."""
+    return synthetic_state_dict(param_specs(CVIT_FAMILY[name], **kw), seed)
+
+
+# the four families' earlier entry points (each only takes its own names)
+def repbn8_param_specs(**kw):
+    return param_specs(CVIT_FAMILY[REPBN8_NAME], **kw)
+
+
+def variant_param_specs(name: str, **kw):
+    return param_specs(VARIANTS[name], **kw)
+
+
+def dconv_param_specs(**kw):
+    return param_specs(CVIT_FAMILY[DCONV_NAME], **kw)
+
+
+def other_param_specs(name: str, **kw):
+    return param_specs(OTHER_VARIANTS[name], **kw)
+
+
+def make_repbn8_state_dict(seed: int = 0, **kw):
+    return make_family_state_dict(REPBN8_NAME, seed, **kw)
+
+
+def make_variant_state_dict(name: str, seed: int = 0, **kw):
+    return synthetic_state_dict(variant_param_specs(name, **kw), seed)
+
+
+def make_dconv_state_dict(seed: int = 0, **kw):
+    return make_family_state_dict(DCONV_NAME, seed, **kw)
+
+
+def make_other_state_dict(name: str, seed: int = 0, **kw):
+    return synthetic_state_dict(other_param_specs(name, **kw), seed)

@@ -107,7 +107,7 @@ def main(argv=None):
         x = (torch.randn(B, SMFA_HW, SMFA_HW, SMFA_C, generator=g) * 1.5).to(T16[dt]).to(DEV)
         out, cp = torch.empty_like(x), torch.empty_like(x)
         scratch = torch.empty(lib.fac_smfa_scratch_bytes(B, SMFA_HW, SMFA_HW, SMFA_C), dtype=torch.uint8, device=DEV)
-        wpk = smfa._smfa[1]
+        wpk = smfa._smfa
 
         def block():
             _lib.check(lib.fac_smfa(dti, x.data_ptr(), B, SMFA_HW, SMFA_HW, SMFA_C, wpk.data_ptr(), 1, out.data_ptr(),
@@ -133,9 +133,10 @@ def main(argv=None):
             tg = timed_ms(lambda: smfa.ggca_combine16(f7), args.warmup, reps)
         lines.append(f"  for scale: x + GGCA(x) on [{B},7,7,512] {tg[0] * 1e3:8.1f} us")
         convs = []
-        for wp, b, H, ci, co, pl, relu in smfa._layers:
-            if H != SMFA_HW:
+        for s, _run, ops in smfa._steps:
+            if s.kind != "conv" or s.H != SMFA_HW:
                 continue
+            (wp, b), H, ci, co, pl, relu = ops, s.H, s.ci, s.co, s.pool, s.relu
             xi = (torch.rand(B, H, H, ci, generator=g) * 3).to(T16[dt]).to(DEV)
             yo = torch.empty(B, H // 2 if pl else H, H // 2 if pl else H, co, dtype=T16[dt], device=DEV)
 
