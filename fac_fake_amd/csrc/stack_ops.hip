@@ -100,6 +100,8 @@ int fac_conv3x3(int dtype, const void* in, const void* wpk, const float* bias, v
                 int cout, int pool, int relu, const void* zero256, void* stream) {
   if (!in || !wpk || !bias || !out || !zero256 || n <= 0 || (dtype != 0 && dtype != 1)) return FAC_ERR_ARG;
   if (!fac::conv3x3_shape_ok(h, cin, cout)) return FAC_ERR_SHAPE;
+  // the 14x14 / BN 192 tile has no fused-pool instantiation (conv.hip, launch_box POOLED = false)
+  if (pool && h == 14 && fac::conv_block_n(h, cout) == 192) return FAC_ERR_SHAPE;
   const hipError_t e = fac::launch_conv3x3(dtype, (const uint16_t*)in, (const uint16_t*)wpk, bias, (uint16_t*)out, n,
                                            h, h, cin, cout, pool != 0, (const uint16_t*)zero256,
                                            (hipStream_t)stream, relu != 0);

@@ -425,8 +425,10 @@ int fac_ew(int dtype, int op, const void* a, int lda, int a_off, const void* b, 
  * GEMM of conv.hip: in [n][h][h][cin] -> out [n][h'][h'][cout] (h' = h/2 with
  * pool); h in {112, 56, 28, 14} (224: cout 32, the unfused kernel), cin a
  * multiple of 32, cout a multiple of one of the resolution's blocks (64 at
- * 112; 128 or 64 at 56; 256, 192 or 128 at 28; 128 at 14 — the largest that
- * divides cout is used).  wpk: fac_conv3x3_pack of the folded fp32 weight
+ * 112; 128 or 64 at 56; 256, 192 or 128 at 28; 128, 192 or 64 at 14 — the
+ * first of these, in the order given, that divides cout is used).  The 192
+ * block at 14 has no fused pool: pool = 1 with such a cout (a multiple of 192
+ * and not of 128) is FAC_ERR_SHAPE.  wpk: fac_conv3x3_pack of the folded fp32 weight
  * [cout][cin][3][3]; bias fp32 [cout]; zero256: 256 zero bytes of device
  * memory (the source of zero-padding loads).
  * fac_conv3x3_packed_elems: 16-bit elements of the packed weight (0: shape

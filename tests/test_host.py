@@ -241,14 +241,18 @@ def test_sharding_bounds():
             assert max(sizes) - min(sizes) <= 1
 
 
-@pytest.mark.parametrize("H,ci,co", [(224, 32, 32), (112, 64, 64), (56, 128, 128), (28, 256, 256), (14, 512, 512)])
+@pytest.mark.parametrize("H,ci,co", [(224, 32, 32), (112, 64, 64), (56, 128, 128), (28, 256, 256), (14, 512, 512),
+                                     (56, 64, 64), (28, 96, 192), (28, 32, 128), (14, 64, 192), (14, 32, 320)])
 def test_conv3x3_weight_packing_layout(built_lib, H, ci, co):
     """fac_conv3x3_pack (host code, stack_ops.hip): [n-block][chunk][tap][q][BN][8]
-    with BN = conv_block_n(H); below 224 the 16-byte pieces of the odd-kernel-row
-    taps are stored as q ^ 2, matching conv.hip's row-parity-swizzled halo."""
+    with BN = conv_block_n(H, co), the resolution's largest block or, for an
+    output width that one does not divide, the next that does; below 224 the
+    16-byte pieces of the odd-kernel-row taps are stored as q ^ 2, matching
+    conv.hip's row-parity-swizzled halo."""
     from fac_fake_amd import _lib
     lib = _lib.load()
     bn = {224: 32, 112: 64, 56: 128, 28: 256, 14: 128}[H]
+    bn = {(56, 64): 64, (28, 192): 192, (28, 128): 128, (14, 192): 192, (14, 320): 64}.get((H, co), bn)
     n = lib.fac_conv3x3_packed_elems(H, ci, co)
     assert n == co * ci * 9
     w = (torch.arange(co * ci * 9, dtype=torch.float32) % 2039).reshape(co, ci, 3, 3) / 1024.0
@@ -262,6 +266,29 @@ def test_conv3x3_weight_packing_layout(built_lib, H, ci, co):
                     qs = q ^ 2 if (H != 224 and (t // 3) % 2 == 1) else q
                     want = w[nb * bn:(nb + 1) * bn, ch * 32 + qs * 8:ch * 32 + qs * 8 + 8].reshape(bn, 8, 9)[:, :, t]
                     assert torch.equal(got[nb, ch, t, q], want), (nb, ch, t, q)
+
+
+def test_stem224_conv1_packing_layout(built_lib):
+    """fac_stem224_pack_conv1 (host code, stack_ops.hip): [32][64], element
+    o*64 + ((ky*2 + kx/2)*2 + kx%2)*4 + c holds w[o][c][ky][kx] (one 16-byte lane
+    chunk = two horizontally adjacent taps of four channels); everything else,
+    the fourth channel, the kx = 3 slots and k >= 48, is zero."""
+    from fac_fake_amd import _lib
+    lib = _lib.load()
+    w = (1.0 + torch.arange(32 * 3 * 9, dtype=torch.float32)).reshape(32, 3, 3, 3) / 1024.0   # distinct, none zero
+    for dti, td in ((1, torch.float16), (0, torch.bfloat16)):
+        out = torch.full((32 * 64,), 0x5A5A, dtype=torch.int16)
+        _lib.check(lib.fac_stem224_pack_conv1(dti, w.data_ptr(), out.data_ptr()), None, "pack_conv1")
+        got = out.view(td).float().reshape(32, 64)
+        want = torch.zeros(32, 64)
+        for o in range(32):
+            for c in range(3):
+                for ky in range(3):
+                    for kx in range(3):
+                        want[o, ((ky * 2 + kx // 2) * 2 + kx % 2) * 4 + c] = w[o, c, ky, kx].to(td).float()
+        assert int((want != 0).sum()) == 32 * 27
+        assert torch.equal(got, want)
+        assert bool((out.reshape(32, 64)[want == 0] == 0).all())      # +0, not just == 0
 
 
 def test_reference_mask_semantics(golden):
