@@ -20,6 +20,9 @@ there).  ``VariantCViT`` is the one class body for all of them:
              folded on the host, the 2x2 max-pool and the ReLU in its epilogue;
     idw      ``fac_idwconv``: InceptionDWConv2d -> BatchNorm -> ReLU (-> pool);
     smfa     ``fac_smfa``: x + SMFA(x), with a scratch buffer kept per model;
+    bfm      BFM(x, x) = 4 (ReLU conv3 + ReLU conv5 + ReLU conv7)(x) on the route
+             ``bfm.bfm_prepare`` gives (three ``fac_conv_nd`` + ``fac_ew``, or
+             one ``fac_bfm``), the entries of ``weights.BFM_VARIANTS`` (bfm.py);
     ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
              (GGCA(x)) at the entry's site;
 
@@ -51,7 +54,7 @@ from torch import nn
 from . import _lib
 from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
 from .ops import TORCH16, fold_bn, pack_input
-from .weights import CVIT_FAMILY, FAMILY_NAMES, REPBN8_NAME, VARIANT_NAMES, VARIANTS, param_specs
+from .weights import BFM_VARIANTS, CVIT_FAMILY, REPBN8_NAME, VARIANT_NAMES, VARIANTS, family_entry, param_specs
 
 SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048)
@@ -128,25 +131,29 @@ def _pos_index(B: int, pos_index, device) -> torch.Tensor:
 
 # One launch of the stem.  labels: the values of stem_features' `upto` that stop
 # right after it ("after n entries of the table's layers", "features1", "smfa",
-# "ggca"); H: the side of the map it runs on; ci, co: its input / output channels;
+# "ggca", "bfm"); H: the side of the map it runs on; ci, co: its input / output channels;
 # pool, relu: fac_conv3x3's and fac_idwconv's epilogue; op: the ggca step's GGCA_OPS name.
 Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, False, None))
 
 
 def stem_plan(entry) -> list:
-    """The launches of one CVIT_FAMILY entry's conv stem, in order (kinds: the
-    module docstring's).  The first block is the fused stem224 if and only if
-    the entry's first three layers are convs or DEConvs."""
+    """The launches of one CVIT_FAMILY or BFM_VARIANTS entry's conv stem, in
+    order (kinds: the module docstring's).  The first block is the fused stem224
+    if and only if the entry's first three layers are convs or DEConvs.  Where
+    several blocks follow one sequential they run smfa, ggca, bfm."""
     layers = entry["layers"]
     seqs = [l[0] for l in layers]
     end = lambda s: len(layers) if s == "stem" else max(i for i, q in enumerate(seqs) if q == s) + 1  # noqa: E731
     ggca_at = end(entry["ggca"][0]) if entry["ggca"] is not None else None
     smfa_at = end(entry["smfa"]) if entry["smfa"] is not None else None
+    bfm = entry.get("bfm")
+    bfm_at = end(bfm[0]) if bfm is not None else None
     f1 = end(seqs[0])
     fused = all(l[2] != "idw" for l in layers[:3])
     if fused:
         assert [l[3:5] + l[6:] for l in layers[:3]] == [(3, 32, True, False), (32, 32, True, False),
-                                                         (32, 32, True, True)] and min(f1, ggca_at or 4, smfa_at or 4) > 3
+                                                         (32, 32, True, True)] and \
+            min(f1, ggca_at or 4, smfa_at or 4, bfm_at or 4) > 3
         plan, H, done = [Step("stem224", (3,), 224, 3, 32, True, True)], 112, 3
     else:
         plan, H, done = [Step("pack32", (), 224, 3, 32)], 224, 0
@@ -163,6 +170,9 @@ def stem_plan(entry) -> list:
         if n == ggca_at:
             C, Hg, _W = entry["ggca"][1]
             plan.append(Step("ggca", ("ggca",), Hg, C, C, op=entry["ggca"][2]))
+        if n == bfm_at:
+            assert co == bfm[1], (co, bfm)
+            plan.append(Step("bfm", ("bfm",), H, co, co))
     return plan
 
 
@@ -170,7 +180,7 @@ def steps_upto(plan, upto) -> int:
     """How many steps of `plan` run for stem_features' `upto`: None all of them;
     an int n up to and including the n-th entry of the table's layers;
     "features1" the first sequential, before the block that follows it; "smfa" /
-    "ggca" that combine.  ValueError where the plan has no such stop: an int
+    "ggca" / "bfm" that block.  ValueError where the plan has no such stop: an int
     inside the fused first block or past the last layer, a block the class lacks."""
     if upto is None:
         return len(plan)
@@ -193,7 +203,7 @@ class VariantCViT(nn.Module):
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        if self.variant not in CVIT_FAMILY:
+        if self.variant not in CVIT_FAMILY and self.variant not in BFM_VARIANTS:
             raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -203,7 +213,7 @@ class VariantCViT(nn.Module):
             raise ValueError(f"dtype must be one of {list(_lib.DTYPES)}")
         self.dtype_name = dtype
         self.patch_size = patch_size
-        self.table = CVIT_FAMILY[self.variant]
+        self.table = family_entry(self.variant)
         for name, shape, kind in param_specs(self.table, dim=dim, depth=depth, mlp_dim=mlp_dim,
                                              num_classes=num_classes, channels=channels, patch_size=patch_size):
             *path, leaf = name.split(".")
@@ -301,12 +311,13 @@ class VariantCViT(nn.Module):
 
     def _prepare_stem(self, sd, device):
         """self._steps: per stem_plan step (step, the class's _step_<kind> function,
-        its device operands); self._ggca / self._smfa: those steps' operands or None."""
+        its device operands); self._ggca / self._smfa / self._bfm: those steps' operands or None."""
+        from .bfm import bfm_fold, bfm_prepare
         from .other import smfa16, smfa_fold, smfa_pack
         self._smfa16 = smfa16          # bound here: other.py imports this module
         folded = list(self._fold(sd))
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
-        self._ggca = self._smfa = None
+        self._ggca = self._smfa = self._bfm = None
         self._steps = []
         for s in stem_plan(self.table):
             if s.kind == "stem224":
@@ -321,6 +332,8 @@ class VariantCViT(nn.Module):
                 ops = tuple(t.to(device) for t in folded[s.labels[0] - 1])
             elif s.kind == "smfa":
                 ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
+            elif s.kind == "bfm":
+                ops = self._bfm = bfm_prepare(bfm_fold(sd), self.dtype_name, device)
             elif s.kind == "ggca":
                 g = "ggca.shared_conv."
                 cr, cg = sd[g + "0.weight"].shape[:2]
@@ -427,6 +440,9 @@ class VariantCViT(nn.Module):
     def _step_ggca(self, x, s, ops, u8, st):
         return self.ggca_combine16(x)
 
+    def _step_bfm(self, x, s, ops, u8, st):
+        return ops(x)
+
     def ggca_combine16(self, f: torch.Tensor) -> torch.Tensor:
         """The class's GGCA step on [B,H,W,C] 16-bit NHWC: x * GGCA(x), x + GGCA(x) or GGCA(x)."""
         _site, (C, H, W), op = self.table["ggca"]
@@ -499,8 +515,7 @@ _MODULES = {REPBN8_NAME: "repbn8"}   # classes with methods of their own live in
 
 def variant_class(name: str) -> type:
     """The drop-in class of reference file ``model/<name>.py`` or ``model/other/<name>.py`` (its ``CViT``)."""
-    if name not in CVIT_FAMILY:
-        raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES)}")
+    family_entry(name)       # KeyError for a name of neither table
     if name not in _CLASSES:
         if name in _MODULES:
             importlib.import_module(f"{__package__}.{_MODULES[name]}")

@@ -1025,8 +1025,66 @@ CVIT_FAMILY = {
 FAMILY_NAMES = tuple(CVIT_FAMILY)
 
 
+# ---------------------------------------------------------------- CViT model/other/ with BFM
+# CViT-main/model/other/cvit_GGCA4_BFM5.py: cvit_GGCA4 plus x = BFM(512)(x, x)
+# on the stem's 512x7x7 output (:260-272: a MultiScaleFeatureExtractor of three
+# full C -> C convs, 3x3, 5x5 and 7x7, each ReLU'd, summed; then TFAM, which on
+# two identical inputs is a factor 4 whatever its weights: bfm.py).  A
+# table of its own: CVIT_FAMILY's entries have exactly five keys.  An entry is a
+# CVIT_FAMILY entry plus
+#   bfm      (site, C): site "stem" (after the last sequential) or the sequential
+#            the block follows ("features1" with C = 256 is cvit_BFM_MDFA's
+#            spelling, which no entry uses yet).
+BFM_VARIANTS = {
+    "cvit_GGCA4_BFM5": dict(OTHER_VARIANTS["cvit_GGCA4"], bfm=("stem", 512)),
+}
+BFM_NAMES = tuple(BFM_VARIANTS)
+# Synthetic BFM weights.  The three convs are He-uniform times BFM_GAIN (the
+# block sums three ReLU'd convs and multiplies by 4, so without a gain it would
+# multiply its input's norm by about ten), their biases are drawn in
+# +-BFM_BIAS and the eight TFAM tensors, which cannot change the output, in
+# +-[0.1, 0.5].  tools/make_golden_bfm.py asserts on the 4 golden crops that
+# ||BFM(f)|| / ||f|| lies in 0.25..4, that at least a quarter of the outputs
+# have pre-activations of mixed sign across the three convs, and that no
+# probability saturates.
+BFM_GAIN = 0.25
+BFM_BIAS = 0.1
+BFM_CONVS = (("conv1", 3), ("conv2", 5), ("conv3", 7))      # MultiScaleFeatureExtractor's, with their kernel sizes
+
+
+def bfm_eca_kernel(c: int) -> int:
+    """ChannelAttention's Conv1d kernel size (cvit_GGCA4_BFM5.py:157-159)."""
+    k = int((np.log2(c) + 1) // 2)
+    return k + 1 if k % 2 == 0 else k
+
+
+def _bfm_specs(p, c):
+    specs = []
+    for name, k in BFM_CONVS:
+        specs += [(f"{p}.multi_scale_extractor.{name}.weight", (c, c, k, k), "bfm_conv"),
+                  (f"{p}.multi_scale_extractor.{name}.bias", (c,), "bfm_cbias")]
+    ke = bfm_eca_kernel(c)
+    for name in ("channel_conv1", "channel_conv2"):
+        specs += [(f"{p}.tfam.channel_attention.{name}.weight", (1, 4, ke), "bfm_tfam"),
+                  (f"{p}.tfam.channel_attention.{name}.bias", (1,), "bfm_tfam")]
+    for name in ("spatial_conv1", "spatial_conv2"):
+        specs += [(f"{p}.tfam.spatial_attention.{name}.weight", (1, 4, 7, 7), "bfm_tfam"),
+                  (f"{p}.tfam.spatial_attention.{name}.bias", (1,), "bfm_tfam")]
+    return specs
+
+
+def family_entry(name: str) -> dict:
+    """The table entry of one class: CVIT_FAMILY's, or BFM_VARIANTS'."""
+    if name in CVIT_FAMILY:
+        return CVIT_FAMILY[name]
+    if name in BFM_VARIANTS:
+        return BFM_VARIANTS[name]
+    raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES + BFM_NAMES)}")
+
+
 def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """(name, shape, kind) for every key of one CVIT_FAMILY entry's state_dict, in the reference's order."""
+    """(name, shape, kind) for every key of one CVIT_FAMILY or BFM_VARIANTS entry's state_dict, in the
+    reference's order."""
     specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
     for seq, idx, kind, ci, co, bn, _relu, _pool in entry["layers"]:
         p = f"{seq}.{idx}"
@@ -1066,6 +1124,8 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
         specs += _deconv_specs("Deconv", 256)   # self.Deconv = DEConv(256): in the state_dict, never called
     if entry["smfa"] is not None:
         specs += _smfa_specs("smfa", SMFA_DIM)
+    if entry.get("bfm") is not None:
+        specs += _bfm_specs("bfm", entry["bfm"][1])
     return specs
 
 
@@ -1109,14 +1169,21 @@ def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]"
             sd[key] = _signed(key, shape, seed, 0.5, 1.5)
         elif kind == "smfa_belt":
             sd[key] = _signed(key, shape, seed, 0.5 * SMFA_BELT_GAIN, 1.5 * SMFA_BELT_GAIN)
+        elif kind == "bfm_conv":
+            a = float(BFM_GAIN * np.sqrt(6.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "bfm_cbias":
+            sd[key] = _u(key, shape, seed, -BFM_BIAS, BFM_BIAS)
+        elif kind == "bfm_tfam":
+            sd[key] = _signed(key, shape, seed, 0.1, 0.5)
         else:
             sd[key] = _synthetic(key, shape, kind, seed)
     return sd
 
 
 def make_family_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic weights of the class of reference file `name` (any of FAMILY_NAMES)."""
-    return synthetic_state_dict(param_specs(CVIT_FAMILY[name], **kw), seed)
+    """Synthetic weights of the class of reference file `name` (any of FAMILY_NAMES or BFM_NAMES)."""
+    return synthetic_state_dict(param_specs(family_entry(name), **kw), seed)
 
 
 # the four families' earlier entry points (each only takes its own names)
@@ -1150,3 +1217,11 @@ def make_dconv_state_dict(seed: int = 0, **kw):
 
 def make_other_state_dict(name: str, seed: int = 0, **kw):
     return synthetic_state_dict(other_param_specs(name, **kw), seed)
+
+
+def bfm_param_specs(name: str, **kw):
+    return param_specs(BFM_VARIANTS[name], **kw)
+
+
+def make_bfm_state_dict(name: str, seed: int = 0, **kw):
+    return synthetic_state_dict(bfm_param_specs(name, **kw), seed)

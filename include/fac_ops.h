@@ -526,6 +526,28 @@ int fac_smfa_pack(int dtype, int c, const float* w0, const float* b0, const floa
 int fac_smfa(int dtype, const void* x, int n, int h, int w, int c, const void* wpk, int residual, void* out,
              float* gate_out, void* scratch, void* stream);
 
+/* BFM(x, x) of CViT-main/model/other/cvit_GGCA4_BFM5.py:162-272 (bfm.hip) on
+ * a 16-bit channels-last map x [n][h][w][c] -> out [n][h][w][c]:
+ *   out = scale * (ReLU(conv3(x) + b3) + ReLU(conv5(x) + b5) + ReLU(conv7(x) + b7))
+ * three c -> c convs (3x3, 5x5, 7x7, zero padding 1, 2, 3), each ReLU'd before
+ * the sum; with both inputs the same tensor the reference's TFAM fusion is
+ * exactly scale = 4, whatever its weights.  One launch: one implicit GEMM over
+ * the 7x7 window whose shifted input fragments feed the one, two or three
+ * convs that have a tap at that offset, three fp32 accumulator sets, one
+ * rounding to 16 bits at the store.  fac_bfm_pack (host pointers) takes the
+ * reference's fp32 weights w3 [c][c][3][3], w5 [c][c][5][5], w7 [c][c][7][7]
+ * and writes fac_bfm_packed_elems(c) = 83 c c 16-bit elements (0 for a bad c);
+ * wpk is that array in device memory, bias3 fp32 [3][c] = b3, b5, b7 on the
+ * device.  Every sum is fp32 in a fixed order and nothing is allocated, so a
+ * crop's output does not depend on n and the call can be captured.
+ * FAC_ERR_ARG: a null (x, wpk, bias3, out) or misaligned (16 bytes) pointer,
+ * n <= 0, a bad dtype, out overlapping x (the kernel reads halos);
+ * FAC_ERR_SHAPE: h or w outside 7..14, c not one of 64, 128, 256, 512. */
+size_t fac_bfm_packed_elems(int c);
+int fac_bfm_pack(int dtype, int c, const float* w3, const float* w5, const float* w7, uint16_t* out);
+int fac_bfm(int dtype, const void* x, int n, int h, int w, int c, const void* wpk, const float* bias3, float scale,
+            void* out, void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
