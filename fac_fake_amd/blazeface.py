@@ -403,6 +403,82 @@ class BlazeFace(nn.Module):
                                                 c.data_ptr(), self._stream(dev)), None, "fac_bf_debug_net")
         return b1, b2, r, c
 
+    # ------------------------------------------- one layer kernel at a time
+    @staticmethod
+    def block_shapes(index: int):
+        """((hin, hin, cin), (hout, hout, cout)) of BlazeBlock ``index`` 0..15."""
+        if not 0 <= index < 16:
+            raise ValueError("BlazeBlock index must be 0..15")
+        h = 64
+        for i, (cin, cout, stride) in enumerate(BLOCKS1 + BLOCKS2):
+            if i == index:
+                return (h, h, cin), (h // stride, h // stride, cout)
+            h //= stride
+
+    @staticmethod
+    def _f32_in(x, dev, shape) -> torch.Tensor:
+        x = torch.as_tensor(x)
+        if x.dtype != torch.float32 or tuple(x.shape[1:]) != tuple(shape):
+            raise ValueError(f"expected float32 [T, {', '.join(map(str, shape))}]")
+        return x.to(dev).contiguous()
+
+    @staticmethod
+    def _f32_out(out, dev, shape) -> torch.Tensor:
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if (out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()
+                or tuple(out.shape) != tuple(shape)):
+            raise ValueError(f"out must be a contiguous float32 {tuple(shape)} tensor on {dev}")
+        return out
+
+    def debug_stem(self, x, out=None):
+        """Debug: the stem kernel alone, uint8 tiles -> [b, 64, 64, 24] (NHWC fp32)."""
+        t = self._tiles_u8(x)
+        b, dev = int(t.shape[0]), t.device
+        out = self._f32_out(out, dev, (b, 64, 64, 24))
+        if b:
+            with self._lock:
+                lib = self._ensure(dev)
+                _lib.check(lib.fac_bf_debug_stem(self._h, t.data_ptr(), b, out.data_ptr(), self._stream(dev)),
+                           None, "fac_bf_debug_stem")
+        return out
+
+    def debug_block(self, index: int, x, out=None):
+        """Debug: BlazeBlock ``index`` alone, [b, hin, hin, cin] -> [b, hout, hout, cout] (NHWC fp32)."""
+        sin, sout = self.block_shapes(index)
+        dev = self._work_device(x)
+        if dev.type != "cuda":
+            raise RuntimeError("BlazeFace runs on the GPU only (no CPU fallback): move the model to cuda")
+        x = self._f32_in(x, dev, sin)
+        b = int(x.shape[0])
+        out = self._f32_out(out, dev, (b,) + sout)
+        if b:
+            with self._lock:
+                lib = self._ensure(dev)
+                _lib.check(lib.fac_bf_debug_block(self._h, index, x.data_ptr(), b, out.data_ptr(),
+                                                  self._stream(dev)), None, "fac_bf_debug_block")
+        return out
+
+    def debug_heads(self, b1, b2, out_r=None, out_c=None):
+        """Debug: the heads kernel alone, backbone1 [b, 16, 16, 88] and backbone2
+        [b, 8, 8, 96] -> (r [b, 896, 16], c [b, 896]) in anchor order."""
+        dev = self._work_device(b1)
+        if dev.type != "cuda":
+            raise RuntimeError("BlazeFace runs on the GPU only (no CPU fallback): move the model to cuda")
+        b1 = self._f32_in(b1, dev, (16, 16, 88))
+        b2 = self._f32_in(b2, dev, (8, 8, 96))
+        b = int(b1.shape[0])
+        if int(b2.shape[0]) != b:
+            raise ValueError("b1 and b2 must hold the same tiles")
+        r = self._f32_out(out_r, dev, (b, NUM_ANCHORS, 16))
+        c = self._f32_out(out_c, dev, (b, NUM_ANCHORS))
+        if b:
+            with self._lock:
+                lib = self._ensure(dev)
+                _lib.check(lib.fac_bf_debug_heads(self._h, b1.data_ptr(), b2.data_ptr(), b, r.data_ptr(),
+                                                  c.data_ptr(), self._stream(dev)), None, "fac_bf_debug_heads")
+        return r, c
+
     def predict_on_image(self, img):
         if isinstance(img, np.ndarray):
             img = torch.from_numpy(img).permute((2, 0, 1))

@@ -707,6 +707,34 @@ int fac_bf_debug_net(fac_bf* h, const uint8_t* d_tiles, int T, float* d_b1, floa
   return run_net(h, d_tiles, T, d_b1, d_b2, d_r, d_c, 0.0f, nullptr, nullptr, (hipStream_t)stream);
 }
 
+// One launch each, on the caller's buffers, with the loaded weights: no workspace.
+int fac_bf_debug_stem(fac_bf* h, const uint8_t* d_tiles, int T, float* d_out, void* stream) {
+  if (!h || !d_tiles || !d_out || T <= 0 || T > (1 << 20)) return FAC_ERR_ARG;
+  if (!h->loaded) return FAC_ERR_NOT_LOADED;
+  if (hipSetDevice(h->device) != hipSuccess) return FAC_ERR_HIP;
+  bf_stem<<<T * 4096 / 256, 256, 0, (hipStream_t)stream>>>(d_tiles, h->d_w + h->stem_w, h->d_w + h->stem_b, d_out);
+  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+}
+
+int fac_bf_debug_block(fac_bf* h, int index, const float* d_in, int T, float* d_out, void* stream) {
+  if (!h || !d_in || !d_out || T <= 0 || T > (1 << 20) || index < 0 || index > 15) return FAC_ERR_ARG;
+  if (!h->loaded) return FAC_ERR_NOT_LOADED;
+  if (hipSetDevice(h->device) != hipSuccess) return FAC_ERR_HIP;
+  if (!run_block(index, d_in, h->d_w, h->blk[index], d_out, T, (hipStream_t)stream)) return FAC_ERR_SHAPE;
+  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+}
+
+int fac_bf_debug_heads(fac_bf* h, const float* d_b1, const float* d_b2, int T, float* d_r, float* d_c,
+                       void* stream) {
+  if (!h || !d_b1 || !d_b2 || !d_r || !d_c || T <= 0 || T > (1 << 20)) return FAC_ERR_ARG;
+  if (!h->loaded) return FAC_ERR_NOT_LOADED;
+  if (hipSetDevice(h->device) != hipSuccess) return FAC_ERR_HIP;
+  const float* w = h->d_w;
+  bf_heads<<<dim3(T, 8), 256, 0, (hipStream_t)stream>>>(d_b1, d_b2, w + h->w8, w + h->bias8, w + h->w16,
+                                                         w + h->bias16, d_r, d_c);
+  return hipGetLastError() == hipSuccess ? FAC_OK : FAC_ERR_HIP;
+}
+
 int fac_bf_tile_detections(fac_bf* h, const uint8_t* d_tiles, int T, float min_score, float* d_dets,
                            int32_t* d_counts, void* stream) {
   if (!h || !d_tiles || !d_dets || !d_counts || T <= 0 || T > (1 << 20)) return FAC_ERR_ARG;

@@ -74,6 +74,20 @@ int fac_bf_debug_tiles(fac_bf* h, const uint8_t* d_frames, int F, int H, int W, 
 int fac_bf_debug_net(fac_bf* h, const uint8_t* d_tiles, int T, float* d_b1, float* d_b2, float* d_r, float* d_c,
                      void* stream);
 
+/* Debug: one layer kernel of the net, one launch, on caller-owned buffers with
+ * the loaded weights (no workspace).  NHWC fp32.
+ *   stem   d_tiles uint8 [T, 128, 128, 3] -> d_out [T, 64, 64, 24]
+ *   block  BlazeBlock `index` 0..15 (backbone1.2 .. backbone1.12, then
+ *          backbone2.0 .. backbone2.4): d_in [T, hin, hin, cin] ->
+ *          d_out [T, hin / stride, hin / stride, cout]
+ *   heads  d_b1 [T, 16, 16, 88], d_b2 [T, 8, 8, 96] -> d_r [T, 896, 16],
+ *          d_c [T, 896]
+ * An index outside 0..15 is FAC_ERR_ARG. */
+int fac_bf_debug_stem(fac_bf* h, const uint8_t* d_tiles, int T, float* d_out, void* stream);
+int fac_bf_debug_block(fac_bf* h, int index, const float* d_in, int T, float* d_out, void* stream);
+int fac_bf_debug_heads(fac_bf* h, const float* d_b1, const float* d_b2, int T, float* d_r, float* d_c,
+                       void* stream);
+
 /* Debug: the post-processing of fac_bf_detect from caller-supplied raw
  * tensors of F * n tiles.  d_tile_dets [F * n, 896, 17] and d_tile_counts
  * [F * n] may be NULL; the rest as fac_bf_detect. */

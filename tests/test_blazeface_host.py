@@ -155,6 +155,31 @@ def test_abi_argument_checks(built_lib):
     assert lib.fac_bf_create(0, ctypes.byref(h)) == 0
     t = torch.zeros(4)
     assert lib.fac_bf_tile_detections(h, t.data_ptr(), 1, 0.75, t.data_ptr(), t.data_ptr(), None) == -5  # not loaded
+    # the one-kernel debug entries: null handle / pointer, tile count and block index are argument errors
+    # (checked before the handle's state); good arguments on a handle without weights are "not loaded"
+    p = t.data_ptr()
+    assert lib.fac_bf_debug_stem(None, p, 1, p, None) == -1
+    assert lib.fac_bf_debug_stem(h, None, 1, p, None) == -1
+    assert lib.fac_bf_debug_stem(h, p, 1, None, None) == -1
+    assert lib.fac_bf_debug_stem(h, p, 0, p, None) == -1
+    assert lib.fac_bf_debug_stem(h, p, (1 << 20) + 1, p, None) == -1
+    assert lib.fac_bf_debug_stem(h, p, 1, p, None) == -5
+    assert lib.fac_bf_debug_block(None, 0, p, 1, p, None) == -1
+    assert lib.fac_bf_debug_block(h, 0, None, 1, p, None) == -1
+    assert lib.fac_bf_debug_block(h, 0, p, 1, None, None) == -1
+    assert lib.fac_bf_debug_block(h, 0, p, 0, p, None) == -1
+    assert lib.fac_bf_debug_block(h, 0, p, (1 << 20) + 1, p, None) == -1
+    assert lib.fac_bf_debug_block(h, -1, p, 1, p, None) == -1
+    assert lib.fac_bf_debug_block(h, 16, p, 1, p, None) == -1
+    assert all(lib.fac_bf_debug_block(h, i, p, 1, p, None) == -5 for i in range(16))
+    assert lib.fac_bf_debug_heads(None, p, p, 1, p, p, None) == -1
+    for i in range(4):
+        ptrs = [p, p, p, p]
+        ptrs[i] = None
+        assert lib.fac_bf_debug_heads(h, ptrs[0], ptrs[1], 1, ptrs[2], ptrs[3], None) == -1, i
+    assert lib.fac_bf_debug_heads(h, p, p, 0, p, p, None) == -1
+    assert lib.fac_bf_debug_heads(h, p, p, (1 << 20) + 1, p, p, None) == -1
+    assert lib.fac_bf_debug_heads(h, p, p, 1, p, p, None) == -5
     d = _lib.TensorDesc()
     d.name, d.data, d.ndim = b"backbone1.0.weight", t.data_ptr(), 1
     d.shape[0] = 4
