@@ -23,6 +23,8 @@ there).  ``VariantCViT`` is the one class body for all of them:
     bfm      BFM(x, x) = 4 (ReLU conv3 + ReLU conv5 + ReLU conv7)(x) on the route
              ``bfm.bfm_prepare`` gives (three ``fac_conv_nd`` + ``fac_ew``, or
              one ``fac_bfm``), the entries of ``weights.BFM_VARIANTS`` (bfm.py);
+    mdfa     ``fac_mdfa``: MDFA(x), with a scratch buffer kept per model, the
+             entries of ``weights.MDFA_VARIANTS`` (mdfa.py);
     ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
              (GGCA(x)) at the entry's site;
 
@@ -54,7 +56,8 @@ from torch import nn
 from . import _lib
 from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
 from .ops import TORCH16, fold_bn, pack_input
-from .weights import BFM_VARIANTS, CVIT_FAMILY, REPBN8_NAME, VARIANT_NAMES, VARIANTS, family_entry, param_specs
+from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, REPBN8_NAME, VARIANT_NAMES, VARIANTS, family_entry,
+                      param_specs)
 
 SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048)
@@ -131,16 +134,17 @@ def _pos_index(B: int, pos_index, device) -> torch.Tensor:
 
 # One launch of the stem.  labels: the values of stem_features' `upto` that stop
 # right after it ("after n entries of the table's layers", "features1", "smfa",
-# "ggca", "bfm"); H: the side of the map it runs on; ci, co: its input / output channels;
+# "ggca", "bfm", "mdfa"); H: the side of the map it runs on; ci, co: its input / output channels;
 # pool, relu: fac_conv3x3's and fac_idwconv's epilogue; op: the ggca step's GGCA_OPS name.
 Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, False, None))
 
 
 def stem_plan(entry) -> list:
-    """The launches of one CVIT_FAMILY or BFM_VARIANTS entry's conv stem, in
-    order (kinds: the module docstring's).  The first block is the fused stem224
-    if and only if the entry's first three layers are convs or DEConvs.  Where
-    several blocks follow one sequential they run smfa, ggca, bfm."""
+    """The launches of one CVIT_FAMILY, BFM_VARIANTS or MDFA_VARIANTS entry's
+    conv stem, in order (kinds: the module docstring's).  The first block is the
+    fused stem224 if and only if the entry's first three layers are convs or
+    DEConvs.  Where several blocks follow one sequential they run smfa, ggca,
+    bfm, mdfa (no reference forward has mdfa beside another block at one site)."""
     layers = entry["layers"]
     seqs = [l[0] for l in layers]
     end = lambda s: len(layers) if s == "stem" else max(i for i, q in enumerate(seqs) if q == s) + 1  # noqa: E731
@@ -148,12 +152,14 @@ def stem_plan(entry) -> list:
     smfa_at = end(entry["smfa"]) if entry["smfa"] is not None else None
     bfm = entry.get("bfm")
     bfm_at = end(bfm[0]) if bfm is not None else None
+    mdfa = entry.get("mdfa")
+    mdfa_at = end(mdfa[0]) if mdfa is not None else None
     f1 = end(seqs[0])
     fused = all(l[2] != "idw" for l in layers[:3])
     if fused:
         assert [l[3:5] + l[6:] for l in layers[:3]] == [(3, 32, True, False), (32, 32, True, False),
                                                          (32, 32, True, True)] and \
-            min(f1, ggca_at or 4, smfa_at or 4, bfm_at or 4) > 3
+            min(f1, ggca_at or 4, smfa_at or 4, bfm_at or 4, mdfa_at or 4) > 3
         plan, H, done = [Step("stem224", (3,), 224, 3, 32, True, True)], 112, 3
     else:
         plan, H, done = [Step("pack32", (), 224, 3, 32)], 224, 0
@@ -173,6 +179,9 @@ def stem_plan(entry) -> list:
         if n == bfm_at:
             assert co == bfm[1], (co, bfm)
             plan.append(Step("bfm", ("bfm",), H, co, co))
+        if n == mdfa_at:
+            assert co == mdfa[1], (co, mdfa)
+            plan.append(Step("mdfa", ("mdfa",), H, co, co))
     return plan
 
 
@@ -180,7 +189,7 @@ def steps_upto(plan, upto) -> int:
     """How many steps of `plan` run for stem_features' `upto`: None all of them;
     an int n up to and including the n-th entry of the table's layers;
     "features1" the first sequential, before the block that follows it; "smfa" /
-    "ggca" / "bfm" that block.  ValueError where the plan has no such stop: an int
+    "ggca" / "bfm" / "mdfa" that block.  ValueError where the plan has no such stop: an int
     inside the fused first block or past the last layer, a block the class lacks."""
     if upto is None:
         return len(plan)
@@ -203,7 +212,7 @@ class VariantCViT(nn.Module):
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        if self.variant not in CVIT_FAMILY and self.variant not in BFM_VARIANTS:
+        if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS)):
             raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -231,6 +240,8 @@ class VariantCViT(nn.Module):
         self._ctx = None
         self._smfa_scratch = None          # fac_smfa's scratch, see _scratch_for
         self._smfa_outgrown = []
+        self._mdfa_scratch = None          # fac_mdfa's, the same rule
+        self._mdfa_outgrown = []
         self.eval()
 
     # ------------------------------------------------------------------ weights
@@ -311,13 +322,15 @@ class VariantCViT(nn.Module):
 
     def _prepare_stem(self, sd, device):
         """self._steps: per stem_plan step (step, the class's _step_<kind> function,
-        its device operands); self._ggca / self._smfa / self._bfm: those steps' operands or None."""
+        its device operands); self._ggca / self._smfa / self._bfm / self._mdfa: those steps' operands or None."""
         from .bfm import bfm_fold, bfm_prepare
+        from .mdfa import mdfa16, mdfa_fold, mdfa_pack
+        self._mdfa16 = mdfa16
         from .other import smfa16, smfa_fold, smfa_pack
         self._smfa16 = smfa16          # bound here: other.py imports this module
         folded = list(self._fold(sd))
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
-        self._ggca = self._smfa = self._bfm = None
+        self._ggca = self._smfa = self._bfm = self._mdfa = None
         self._steps = []
         for s in stem_plan(self.table):
             if s.kind == "stem224":
@@ -334,6 +347,8 @@ class VariantCViT(nn.Module):
                 ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
             elif s.kind == "bfm":
                 ops = self._bfm = bfm_prepare(bfm_fold(sd), self.dtype_name, device)
+            elif s.kind == "mdfa":
+                ops = self._mdfa = mdfa_pack(mdfa_fold(sd), self.dtype_name, device)
             elif s.kind == "ggca":
                 g = "ggca.shared_conv."
                 cr, cg = sd[g + "0.weight"].shape[:2]
@@ -390,6 +405,16 @@ class VariantCViT(nn.Module):
             self._smfa_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
         return buf
 
+    def _mdfa_scratch_for(self, B: int, s: Step, device) -> torch.Tensor:
+        """fac_mdfa's scratch for B crops, kept and grown like _scratch_for's."""
+        need = _lib.load().fac_mdfa_scratch_bytes(B, s.H, s.H, s.co)
+        buf = self._mdfa_scratch
+        if buf is None or buf.numel() < need or buf.device != torch.device(device):
+            if buf is not None:
+                self._mdfa_outgrown.append(buf)
+            self._mdfa_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
+        return buf
+
     def reserve(self, max_batch: int, device=None):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._prepare(dev)
@@ -397,6 +422,8 @@ class VariantCViT(nn.Module):
         for s, _run, ops in self._steps:
             if s.kind == "smfa":
                 self._scratch_for(int(max_batch), s, ops.device)
+            elif s.kind == "mdfa":
+                self._mdfa_scratch_for(int(max_batch), s, ops.device)
 
     # ------------------------------------------------------------------ the stem's launches
     # _step_<kind>(x, s, ops, u8, st) -> the step's output, a new tensor; x: the
@@ -442,6 +469,9 @@ class VariantCViT(nn.Module):
 
     def _step_bfm(self, x, s, ops, u8, st):
         return ops(x)
+
+    def _step_mdfa(self, x, s, ops, u8, st):
+        return self._mdfa16(x, ops, self.dtype_name, scratch=self._mdfa_scratch_for(x.shape[0], s, x.device))
 
     def ggca_combine16(self, f: torch.Tensor) -> torch.Tensor:
         """The class's GGCA step on [B,H,W,C] 16-bit NHWC: x * GGCA(x), x + GGCA(x) or GGCA(x)."""

@@ -1034,7 +1034,7 @@ FAMILY_NAMES = tuple(CVIT_FAMILY)
 # CVIT_FAMILY entry plus
 #   bfm      (site, C): site "stem" (after the last sequential) or the sequential
 #            the block follows ("features1" with C = 256 is cvit_BFM_MDFA's
-#            spelling, which no entry uses yet).
+#            spelling, an entry of MDFA_VARIANTS below).
 BFM_VARIANTS = {
     "cvit_GGCA4_BFM5": dict(OTHER_VARIANTS["cvit_GGCA4"], bfm=("stem", 512)),
 }
@@ -1073,18 +1073,70 @@ def _bfm_specs(p, c):
     return specs
 
 
+# ---------------------------------------------------------------- CViT model/other/ with MDFA
+# CViT-main/model/other/cvit_GGCA4_MDFA5.py, cvit_MDFA_BFM.py and
+# cvit_BFM_MDFA.py: the (4, 1) plain stem with x = MDFA(C, C)(x) (:158-261 of
+# the first: a 1x1 and three dilated 3x3 conv branches, a global branch, the
+# hebing gate and conv_cat; mdfa.py) on a feature map, and GGCA or BFM at the
+# other site.  A table of its own, looked up third.  An entry is a CVIT_FAMILY
+# entry plus
+#   mdfa         (site, C), spelled like bfm's;
+#   bfm          (site, C) where the class has the block;
+#   ggca_unused  (C, H, W) of a self.ggca that is in the state_dict and never
+#                called (the entry's ggca is then None), like deconv's Deconv.
+# The reference classes define ggca, mdfa, bfm in that order.
+_MDFA_BASE = dict(OTHER_VARIANTS["cvit_GGCA4"], ggca=None)
+MDFA_VARIANTS = {
+    "cvit_GGCA4_MDFA5": dict(_MDFA_BASE, ggca=("stem", (512, 7, 7), "att"), mdfa=("features1", 256)),
+    "cvit_MDFA_BFM": dict(_MDFA_BASE, mdfa=("features1", 256), bfm=("stem", 512), ggca_unused=(256, 14, 14)),
+    "cvit_BFM_MDFA": dict(_MDFA_BASE, mdfa=("stem", 512), bfm=("features1", 256), ggca_unused=(256, 14, 14)),
+}
+MDFA_NAMES = tuple(MDFA_VARIANTS)
+# Synthetic MDFA weights.  The six convs are He-uniform times MDFA_GAIN with
+# biases in +-MDFA_BIAS, the six BatchNorms are the family's randomised
+# statistics.  PyTorch's default init of the two gate vectors leaves the
+# channel gate t_b below the pixel gate s_p everywhere, which would hide one
+# side of max(t_b, s_p): here kongjian's w_s is symmetric with a gain that
+# spreads s_p over (0, 1), and tongdao's w_t is drawn in [0, 2 MDFA_T_MEAN[C] /
+# 5C) so that t_b lands inside that spread.  tools/make_golden_mdfa.py asserts
+# on the 4 golden crops of every class that each side of the max wins on at
+# least 20 % of the pixels, that ||MDFA(f)|| / ||f|| lies in 0.25..4, that
+# max cat <= 64 and that no probability saturates.
+MDFA_GAIN = {"branch1.0": 0.7, "branch2.0": 0.7, "branch3.0": 0.7, "branch4.0": 0.7, "branch5_conv": 1.0}
+MDFA_CAT_GAIN = {256: 1.0, 512: 0.4}     # conv_cat's, per width: MDFA(512) sees the larger map that follows BFM(256)
+MDFA_BIAS = 0.1
+MDFA_S_GAIN = 0.25         # w_s in +-MDFA_S_GAIN sqrt(3 / 5C)
+MDFA_T_MEAN = {256: 0.329, 512: 0.397}   # other widths (the block tests' small maps): 1
+
+
+def _mdfa_specs(p, c):
+    specs = []
+    for i, k in ((1, 1), (2, 3), (3, 3), (4, 3)):
+        specs += [(f"{p}.branch{i}.0.weight", (c, c, k, k), "mdfa_conv"), (f"{p}.branch{i}.0.bias", (c,), "mdfa_cbias")]
+        specs += _bn_specs(f"{p}.branch{i}.1", c)
+    specs += [(f"{p}.branch5_conv.weight", (c, c, 1, 1), "mdfa_conv"), (f"{p}.branch5_conv.bias", (c,), "mdfa_cbias")]
+    specs += _bn_specs(f"{p}.branch5_bn", c)
+    specs += [(f"{p}.conv_cat.0.weight", (c, 5 * c, 1, 1), "mdfa_conv"), (f"{p}.conv_cat.0.bias", (c,), "mdfa_cbias")]
+    specs += _bn_specs(f"{p}.conv_cat.1", c)
+    specs += [(f"{p}.Hebing.tongdao.fc.weight", (1, 5 * c, 1, 1), "mdfa_wt"),
+              (f"{p}.Hebing.kongjian.Conv1x1.weight", (1, 5 * c, 1, 1), "mdfa_ws")]
+    return specs
+
+
 def family_entry(name: str) -> dict:
-    """The table entry of one class: CVIT_FAMILY's, or BFM_VARIANTS'."""
+    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS' or MDFA_VARIANTS'."""
     if name in CVIT_FAMILY:
         return CVIT_FAMILY[name]
     if name in BFM_VARIANTS:
         return BFM_VARIANTS[name]
-    raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES + BFM_NAMES)}")
+    if name in MDFA_VARIANTS:
+        return MDFA_VARIANTS[name]
+    raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES)}")
 
 
 def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
-    """(name, shape, kind) for every key of one CVIT_FAMILY or BFM_VARIANTS entry's state_dict, in the
-    reference's order."""
+    """(name, shape, kind) for every key of one CVIT_FAMILY, BFM_VARIANTS or MDFA_VARIANTS entry's
+    state_dict, in the reference's order."""
     specs = [("pos_embedding", (32, 1, dim), "emb"), ("cls_token", (1, 1, dim), "emb")]
     for seq, idx, kind, ci, co, bn, _relu, _pool in entry["layers"]:
         p = f"{seq}.{idx}"
@@ -1113,8 +1165,9 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
                   (f"{p}.1.fn.fn.net.2.weight", (dim, mlp_dim), "lin"), (f"{p}.1.fn.fn.net.2.bias", (dim,), "lbias")]
     specs += [("mlp_head.0.weight", (mlp_dim, dim), "lin"), ("mlp_head.0.bias", (mlp_dim,), "lbias"),
               ("mlp_head.2.weight", (num_classes, mlp_dim), "head"), ("mlp_head.2.bias", (num_classes,), "lbias")]
-    if entry["ggca"] is not None:
-        gc = entry["ggca"][1][0] // 4           # GGCA(C, H, W): 4 groups, reduction 16
+    ggca_chw = entry["ggca"][1] if entry["ggca"] is not None else entry.get("ggca_unused")
+    if ggca_chw is not None:
+        gc = ggca_chw[0] // 4                   # GGCA(C, H, W): 4 groups, reduction 16
         specs += [("ggca.shared_conv.0.weight", (gc // 16, gc, 1, 1), "conv"),
                   ("ggca.shared_conv.0.bias", (gc // 16,), "cbias")]
         specs += _bn_specs("ggca.shared_conv.1", gc // 16)
@@ -1124,6 +1177,8 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
         specs += _deconv_specs("Deconv", 256)   # self.Deconv = DEConv(256): in the state_dict, never called
     if entry["smfa"] is not None:
         specs += _smfa_specs("smfa", SMFA_DIM)
+    if entry.get("mdfa") is not None:
+        specs += _mdfa_specs("mdfa", entry["mdfa"][1])
     if entry.get("bfm") is not None:
         specs += _bfm_specs("bfm", entry["bfm"][1])
     return specs
@@ -1176,13 +1231,25 @@ def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]"
             sd[key] = _u(key, shape, seed, -BFM_BIAS, BFM_BIAS)
         elif kind == "bfm_tfam":
             sd[key] = _signed(key, shape, seed, 0.1, 0.5)
+        elif kind == "mdfa_conv":
+            part = key[len("mdfa."):-len(".weight")]
+            gain = MDFA_CAT_GAIN.get(shape[0], 1.0) if part == "conv_cat.0" else MDFA_GAIN[part]
+            a = float(gain * np.sqrt(6.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "mdfa_cbias":
+            sd[key] = _u(key, shape, seed, -MDFA_BIAS, MDFA_BIAS)
+        elif kind == "mdfa_ws":
+            a = float(MDFA_S_GAIN * np.sqrt(3.0 / shape[1]))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "mdfa_wt":
+            sd[key] = _u(key, shape, seed, 0.0, 2.0 * MDFA_T_MEAN.get(shape[1] // 5, 1.0) / shape[1])
         else:
             sd[key] = _synthetic(key, shape, kind, seed)
     return sd
 
 
 def make_family_state_dict(name: str, seed: int = 0, **kw) -> "OrderedDict[str, np.ndarray]":
-    """Synthetic weights of the class of reference file `name` (any of FAMILY_NAMES or BFM_NAMES)."""
+    """Synthetic weights of the class of reference file `name` (any of FAMILY_NAMES, BFM_NAMES or MDFA_NAMES)."""
     return synthetic_state_dict(param_specs(family_entry(name), **kw), seed)
 
 
@@ -1225,3 +1292,11 @@ def bfm_param_specs(name: str, **kw):
 
 def make_bfm_state_dict(name: str, seed: int = 0, **kw):
     return synthetic_state_dict(bfm_param_specs(name, **kw), seed)
+
+
+def mdfa_param_specs(name: str, **kw):
+    return param_specs(MDFA_VARIANTS[name], **kw)
+
+
+def make_mdfa_state_dict(name: str, seed: int = 0, **kw):
+    return synthetic_state_dict(mdfa_param_specs(name, **kw), seed)

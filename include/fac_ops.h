@@ -548,6 +548,39 @@ int fac_bfm_pack(int dtype, int c, const float* w3, const float* w5, const float
 int fac_bfm(int dtype, const void* x, int n, int h, int w, int c, const void* wpk, const float* bias3, float scale,
             void* out, void* stream);
 
+/* MDFA(c, c) of CViT-main/model/other/cvit_GGCA4_MDFA5.py:158-261 (mdfa.hip)
+ * on a 16-bit channels-last map x [n][h][w][c] -> out [n][h][w][c]: a 1x1 and
+ * three 3x3 conv branches with padding = dilation = 6, 12, 18, each with its
+ * eval BatchNorm folded and a ReLU; a fifth branch g = ReLU(W5 mean_p x + b5)
+ * per crop; cat = [b1 b2 b3 b4 g]; m_p = max(ReLU(w_t . mean_p cat),
+ * sigmoid(w_s . cat_p)); out = ReLU(m_p (Wcat . cat_p^2) + bcat).  That is the
+ * reference's max(tongdao(cat), kongjian(cat)) * cat through conv_cat, exactly,
+ * because cat >= 0.  Taps that lie outside an h x w map for every pixel are
+ * dropped when the launch is planned.
+ * fac_mdfa_pack (host pointers, fp32 in, BatchNorm already folded) takes w1
+ * [c][c], w2 w3 w4 [c][c][3][3] (dilation 6, 12, 18), bias4 [4][c], w5 [c][c],
+ * b5 [c], wcat [c][5c], bcat [c], ws [5c] (kongjian), wt [5c] (tongdao) and
+ * writes fac_mdfa_packed_bytes(c) bytes (0 for a bad c): w1..w4 and
+ * wcat[:, :4c] become 16-bit MFMA operands, the rest stays fp32.  packed is
+ * that blob in device memory.  scratch: fac_mdfa_scratch_bytes(n, h, w, c)
+ * bytes (0 for a bad shape); the call allocates nothing, runs four launches on
+ * `stream` and can be captured.
+ * Rounding: the 16-bit input and weights; the branch sums, bias, ReLU, both
+ * dots, the crop means, g, its share of conv_cat, the sigmoid and m_p are fp32
+ * in a fixed order without atomics, so a crop's output does not depend on n;
+ * cat^2 is rounded once to 16 bits as the conv_cat operand (fp16: clamped to
+ * 65504, so no inf or NaN is produced); the output is rounded once.
+ * FAC_ERR_ARG: a null (x, packed, out, scratch) or misaligned (16 bytes)
+ * pointer, n <= 0, a bad dtype, out overlapping x; FAC_ERR_SHAPE: h or w
+ * outside 7..14, c not one of 64, 128, 256, 512. */
+size_t fac_mdfa_packed_bytes(int c);
+size_t fac_mdfa_scratch_bytes(int n, int h, int w, int c);
+int fac_mdfa_pack(int dtype, int c, const float* w1, const float* w2, const float* w3, const float* w4,
+                  const float* bias4, const float* w5, const float* b5, const float* wcat, const float* bcat,
+                  const float* ws, const float* wt, void* out);
+int fac_mdfa(int dtype, const void* x, int n, int h, int w, int c, const void* packed, void* out, void* scratch,
+             void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
