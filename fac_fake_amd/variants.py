@@ -25,6 +25,9 @@ there).  ``VariantCViT`` is the one class body for all of them:
              one ``fac_bfm``), the entries of ``weights.BFM_VARIANTS`` (bfm.py);
     mdfa     ``fac_mdfa``: MDFA(x), with a scratch buffer kept per model, the
              entries of ``weights.MDFA_VARIANTS`` (mdfa.py);
+    scconv   ``fac_scconv``: ScConv -> BatchNorm -> ReLU (-> pool), with one
+             scratch buffer kept per model for its sites, the entries of
+             ``weights.SCCONV_VARIANTS`` (scconv.py);
     ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
              (GGCA(x)) at the entry's site;
 
@@ -56,8 +59,8 @@ from torch import nn
 from . import _lib
 from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
 from .ops import TORCH16, fold_bn, pack_input
-from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, REPBN8_NAME, VARIANT_NAMES, VARIANTS, family_entry,
-                      param_specs)
+from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, REPBN8_NAME, SCCONV_VARIANTS, VARIANT_NAMES, VARIANTS,
+                      family_entry, param_specs)
 
 SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048)
@@ -140,7 +143,7 @@ Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, F
 
 
 def stem_plan(entry) -> list:
-    """The launches of one CVIT_FAMILY, BFM_VARIANTS or MDFA_VARIANTS entry's
+    """The launches of one CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS or SCCONV_VARIANTS entry's
     conv stem, in order (kinds: the module docstring's).  The first block is the
     fused stem224 if and only if the entry's first three layers are convs or
     DEConvs.  Where several blocks follow one sequential they run smfa, ggca,
@@ -167,6 +170,8 @@ def stem_plan(entry) -> list:
         labels = (n, "features1") if n == f1 else (n,)
         if kind == "idw":
             plan.append(Step("idw", labels, H, co, co, pool, True))
+        elif kind == "sc":
+            plan.append(Step("scconv", labels, H, co, co, pool, True))
         else:
             plan.append(Step("conv", labels, H, 32 if n == 1 else ci, co, pool, relu))
         if pool:
@@ -212,7 +217,7 @@ class VariantCViT(nn.Module):
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS)):
+        if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS)):
             raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -242,10 +247,18 @@ class VariantCViT(nn.Module):
         self._smfa_outgrown = []
         self._mdfa_scratch = None          # fac_mdfa's, the same rule
         self._mdfa_outgrown = []
+        self._scconv_scratch = None        # fac_scconv's, one buffer for all its sites, the same rule
+        self._scconv_outgrown = []
         self.eval()
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        for seq, idx, kind, *_ in self.table["layers"]:
+            g = state_dict.get(f"{seq}.{idx}.SRU.gn.weight") if kind == "sc" else None
+            if g is not None:             # ScConv divides by sum(gamma)
+                tot = float(torch.as_tensor(g).detach().float().sum())
+                if tot == 0.0 or tot != tot or tot in (float("inf"), float("-inf")):
+                    raise ValueError(f"{seq}.{idx}.SRU.gn.weight sums to {tot}: ScConv divides by it")
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
         self._prep = None
         return out
@@ -268,12 +281,17 @@ class VariantCViT(nn.Module):
 
     def _fold(self, sd):
         """Per table layer its operands in fp32 on the host: (weight, bias) with
-        the DEConv and the BatchNorm folded, or dconv.idw_fold's five."""
+        the DEConv and the BatchNorm folded, dconv.idw_fold's five, or
+        scconv.scconv_fold's dict."""
         from .dconv import idw_fold
+        from .scconv import scconv_fold
         for seq, idx, kind, _ci, _co, bn, _relu, _pool in self.table["layers"]:
             p, q = f"{seq}.{idx}", f"{seq}.{bn}"
             if kind == "idw":
                 yield idw_fold(sd, p, q)
+                continue
+            if kind == "sc":
+                yield scconv_fold(sd, p, q)
                 continue
             w, b = (sd[p + ".weight"], sd[p + ".bias"]) if kind == "conv" else deconv_fold(sd, p)
             if bn is not None:
@@ -284,9 +302,12 @@ class VariantCViT(nn.Module):
 
     def folded_layers(self):
         """(weight, bias, relu, pool) per conv; for a table with InceptionDWConv2d
-        layers, ("conv", weight, bias, pool) or ("idw", w_hw, w_w, w_h, scale, shift, pool)."""
+        layers, ("conv", weight, bias, pool) or ("idw", w_hw, w_w, w_h, scale, shift, pool); for one with
+        ScConv layers, ("conv", weight, bias, pool) or ("sc", scconv_fold's dict, pool)."""
         layers = self.table["layers"]
         ops = self._fold(self.state_dict())
+        if any(l[2] == "sc" for l in layers):
+            return [("sc", o, l[7]) if l[2] == "sc" else ("conv", *o, l[7]) for l, o in zip(layers, ops)]
         if any(l[2] == "idw" for l in layers):
             return [("idw" if l[2] == "idw" else "conv", *o, l[7]) for l, o in zip(layers, ops)]
         return [(*o, l[6], l[7]) for l, o in zip(layers, ops)]
@@ -328,6 +349,8 @@ class VariantCViT(nn.Module):
         self._mdfa16 = mdfa16
         from .other import smfa16, smfa_fold, smfa_pack
         self._smfa16 = smfa16          # bound here: other.py imports this module
+        from .scconv import scconv16, scconv_pack
+        self._scconv16 = scconv16
         folded = list(self._fold(sd))
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         self._ggca = self._smfa = self._bfm = self._mdfa = None
@@ -343,6 +366,8 @@ class VariantCViT(nn.Module):
                 ops = (self._packed_conv(w, s.H, device), b.to(device))
             elif s.kind == "idw":
                 ops = tuple(t.to(device) for t in folded[s.labels[0] - 1])
+            elif s.kind == "scconv":
+                ops = scconv_pack(folded[s.labels[0] - 1], self.dtype_name, device)
             elif s.kind == "smfa":
                 ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
             elif s.kind == "bfm":
@@ -415,6 +440,19 @@ class VariantCViT(nn.Module):
             self._mdfa_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
         return buf
 
+    def _scconv_scratch_for(self, B: int, device) -> torch.Tensor:
+        """fac_scconv's scratch for B crops: one buffer sized for the largest of
+        the class's ScConv sites (they run one after the other on one stream), kept
+        and grown like _scratch_for's."""
+        lib = _lib.load()
+        need = max(lib.fac_scconv_scratch_bytes(B, s.H, s.H, s.co) for s, _run, _ops in self._steps if s.kind == "scconv")
+        buf = self._scconv_scratch
+        if buf is None or buf.numel() < need or buf.device != torch.device(device):
+            if buf is not None:
+                self._scconv_outgrown.append(buf)
+            self._scconv_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
+        return buf
+
     def reserve(self, max_batch: int, device=None):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._prepare(dev)
@@ -424,6 +462,8 @@ class VariantCViT(nn.Module):
                 self._scratch_for(int(max_batch), s, ops.device)
             elif s.kind == "mdfa":
                 self._mdfa_scratch_for(int(max_batch), s, ops.device)
+        if any(s.kind == "scconv" for s, _run, _ops in self._steps):
+            self._scconv_scratch_for(int(max_batch), dev)
 
     # ------------------------------------------------------------------ the stem's launches
     # _step_<kind>(x, s, ops, u8, st) -> the step's output, a new tensor; x: the
@@ -459,6 +499,9 @@ class VariantCViT(nn.Module):
                                            s.H, s.co, *[t.data_ptr() for t in ops], int(s.pool), st), None,
                    "fac_idwconv")
         return y
+
+    def _step_scconv(self, x, s, ops, u8, st):
+        return self._scconv16(x, ops, self.dtype_name, pool=s.pool, scratch=self._scconv_scratch_for(x.shape[0], x.device))
 
     def _step_smfa(self, x, s, ops, u8, st):
         return self._smfa16(x, ops, self.dtype_name, residual=True,

@@ -872,7 +872,7 @@ _VARIANT_BLOCKS = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 256, 4), (256, 5
 def _variant_layers(split, kinds: str, bare26: bool = False):
     """The stem's layer list in the REPBN8_LAYERS format.  split: blocks per
     nn.Sequential; kinds: one letter per conv in order, "c" Conv2d or "d"
-    DEConv; bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
+    DEConv, "s" ScConv (SCCONV_VARIANTS); bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
     without BatchNorm or ReLU, a DEConv without BatchNorm (:390-392)."""
     kinds = kinds.replace(" ", "")
     names = ["features"] if len(split) == 1 else [f"features{i + 1}" for i in range(len(split))]
@@ -884,7 +884,7 @@ def _variant_layers(split, kinds: str, bare26: bool = False):
             idx, prev = 0, seq
         convs += 1 if bare26 and bi == 2 else 0
         for li in range(convs):
-            kind = "conv" if kinds[k] == "c" else "deconv"
+            kind = {"c": "conv", "d": "deconv", "s": "sc"}[kinds[k]]
             k += 1
             ci, last = cin if li == 0 else cout, li == convs - 1
             if bare26 and bi == 2 and li == 2:
@@ -1123,15 +1123,65 @@ def _mdfa_specs(p, c):
     return specs
 
 
+# ---------------------------------------------------------------- CViT model/other/ with ScConv
+# CViT-main/model/other/cvit_GGCA_ADD_ScConv.py: the (4, 1) stem with four of
+# its 3x3 convs replaced by ScConv(C) -> BatchNorm -> ReLU (:311-353: a
+# GroupNorm-gated channel exchange, two 1x1 squeezes, a grouped 3x3 + 1x1 and a
+# 1x1 + identity path, rescaled by a softmax over the 2C channel means;
+# scconv.py), at 64x112x112, 128x56x56 and 256x28x28 twice, and x + GGCA(x) on
+# the stem output.  A table of its own, looked up fourth.  An entry is a
+# CVIT_FAMILY entry whose layers may have the kind "sc" (cin = cout = C).
+SCCONV_KINDS = "ccc csc csc cscs cccc"
+SCCONV_VARIANTS = {
+    "cvit_GGCA_ADD_ScConv": _entry(_variant_layers((4, 1), SCCONV_KINDS), _STEM_ADD, "layernorm", False),
+}
+SCCONV_NAMES = tuple(SCCONV_VARIANTS)
+# Synthetic ScConv weights.  The GroupNorm gamma is drawn in [0.5, 1.5] with
+# the sign of every fourth channel negative (both signs, and sum(gamma) about
+# C/2: the reference divides by it, |sum| >= C/4 is asserted), beta in
+# +-[0.2, 0.6] (non-zero; with both signs of t the gate then takes both sides).
+# The five convs are drawn in +-SCCONV_GAIN sqrt(3 / fan_in): the softmax runs
+# over the 2C channel MEANS, which for a post-ReLU input are sums of about C
+# weights, and at the He bound their spread of 2 to 3 makes s peak on a few
+# channels (52 / 2C was measured); at this gain no s exceeds 10 / 2C.  s is
+# about 1 / 2C, so the block shrinks its input by two orders of magnitude: the
+# BatchNorm after a block has running_var drawn around the square of
+# SCCONV_OUT_STD[its prefix] and running_mean around SCCONV_OUT_MEAN[its
+# prefix], both measured block by block on the fixture crops with
+# tools/make_golden_scconv.py --calibrate, so that each layer's output is
+# comparable to its input.  The tool asserts the outcome.
+SCCONV_GAIN = 0.6
+SCCONV_OUT_STD = {"features1.14": 0.02276, "features1.24": 0.003987, "features1.34": 0.001185, "features1.40": 0.0004893}
+SCCONV_OUT_MEAN = {"features1.14": 0.009749, "features1.24": 0.001821, "features1.34": 0.0004308,
+                   "features1.40": 0.0001312}
+
+
+def _scconv_specs(p, c):
+    return [(f"{p}.SRU.gn.weight", (c,), "sc_gamma"), (f"{p}.SRU.gn.bias", (c,), "sc_beta"),
+            (f"{p}.CRU.squeeze1.weight", (c // 4, c // 2, 1, 1), "sc_conv"),
+            (f"{p}.CRU.squeeze2.weight", (c // 4, c // 2, 1, 1), "sc_conv"),
+            (f"{p}.CRU.GWC.weight", (c, c // 8, 3, 3), "sc_conv"), (f"{p}.CRU.GWC.bias", (c,), "cbias"),
+            (f"{p}.CRU.PWC1.weight", (c, c // 4, 1, 1), "sc_conv"),
+            (f"{p}.CRU.PWC2.weight", (3 * c // 4, c // 4, 1, 1), "sc_conv")]
+
+
+def _scconv_bn_specs(p, c):
+    return [(f"{p}.weight", (c,), "gamma"), (f"{p}.bias", (c,), "beta"), (f"{p}.running_mean", (c,), "sc_rmean"),
+            (f"{p}.running_var", (c,), "sc_rvar"), (f"{p}.num_batches_tracked", (), "nbt")]
+
+
 def family_entry(name: str) -> dict:
-    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS' or MDFA_VARIANTS'."""
+    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS', MDFA_VARIANTS' or SCCONV_VARIANTS'."""
     if name in CVIT_FAMILY:
         return CVIT_FAMILY[name]
     if name in BFM_VARIANTS:
         return BFM_VARIANTS[name]
     if name in MDFA_VARIANTS:
         return MDFA_VARIANTS[name]
-    raise KeyError(f"unknown CViT variant {name!r}; known: {', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES)}")
+    if name in SCCONV_VARIANTS:
+        return SCCONV_VARIANTS[name]
+    raise KeyError(f"unknown CViT variant {name!r}; known: "
+                   f"{', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES + SCCONV_NAMES)}")
 
 
 def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
@@ -1142,6 +1192,9 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
         p = f"{seq}.{idx}"
         if kind == "conv":
             specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
+        elif kind == "sc":
+            specs += _scconv_specs(p, co) + _scconv_bn_specs(f"{seq}.{bn}", co)
+            continue
         else:
             specs += _deconv_specs(p, co) if kind == "deconv" else _idw_specs(p, co)
         if bn is not None:
@@ -1241,6 +1294,23 @@ def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]"
         elif kind == "mdfa_ws":
             a = float(MDFA_S_GAIN * np.sqrt(3.0 / shape[1]))
             sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "sc_conv":
+            a = float(SCCONV_GAIN * np.sqrt(3.0 / int(np.prod(shape[1:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "sc_gamma":
+            g = _signed(key, shape, seed, 0.5, 1.5)
+            g = np.abs(g)
+            g[::4] = -g[::4]
+            sd[key] = g.astype(np.float32)
+        elif kind == "sc_beta":
+            sd[key] = _signed(key, shape, seed, 0.2, 0.6)
+        elif kind in ("sc_rmean", "sc_rvar"):
+            bn = key.rsplit(".", 1)[0]
+            std, mean = SCCONV_OUT_STD[bn], SCCONV_OUT_MEAN[bn]
+            if kind == "sc_rmean":
+                sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
+            else:
+                sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
         elif kind == "mdfa_wt":
             sd[key] = _u(key, shape, seed, 0.0, 2.0 * MDFA_T_MEAN.get(shape[1] // 5, 1.0) / shape[1])
         else:
@@ -1300,3 +1370,11 @@ def mdfa_param_specs(name: str, **kw):
 
 def make_mdfa_state_dict(name: str, seed: int = 0, **kw):
     return synthetic_state_dict(mdfa_param_specs(name, **kw), seed)
+
+
+def scconv_param_specs(name: str, **kw):
+    return param_specs(SCCONV_VARIANTS[name], **kw)
+
+
+def make_scconv_state_dict(name: str = "cvit_GGCA_ADD_ScConv", seed: int = 0, **kw):
+    return synthetic_state_dict(scconv_param_specs(name, **kw), seed)

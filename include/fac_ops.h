@@ -581,6 +581,38 @@ int fac_mdfa_pack(int dtype, int c, const float* w1, const float* w2, const floa
 int fac_mdfa(int dtype, const void* x, int n, int h, int w, int c, const void* packed, void* out, void* scratch,
              void* stream);
 
+/* ScConv(c) -> affine(scale, shift) -> ReLU -> optional 2x2 max-pool of
+ * CViT-main/model/other/cvit_GGCA_ADD_ScConv.py:311-353 (scconv.hip) on a 16-bit
+ * channels-last map x [n][h][w][c] -> out [n][h][w][c], pooled [n][h/2][w/2][c]:
+ * GroupNorm(4, c) statistics per crop, the hard gate that moves channels between
+ * the two halves, the two 1x1 squeezes, GWC (3x3, 2 groups, bias) + PWC1 and
+ * [PWC2; identity], and the softmax over the 2c per-crop channel means that
+ * rescales both, the means taken from the linear sums of the squeezed map.
+ * fac_scconv_pack (host pointers, fp32 in) takes gamma, beta [c] (the
+ * GroupNorm's), kc [c] = gamma / sum(gamma), squeeze1, squeeze2 [c/4][c/2], gwc_w
+ * [c][c/8][3][3], gwc_b [c], pwc1 [c][c/4], pwc2 [3c/4][c/4], scale, shift [c]
+ * (the BatchNorm that follows, folded) and writes fac_scconv_packed_bytes(c)
+ * bytes (0 for a bad c): the five conv weights become 16-bit MFMA operands, the
+ * rest stays fp32.  packed is that blob in device memory.  scratch:
+ * fac_scconv_scratch_bytes(n, h, w, c) bytes (0 for a bad shape); the call
+ * allocates nothing, runs six launches on `stream` and can be captured.
+ * stats_out: null, or device fp32 [n][4][2] that receives (mu_g, 1 / sqrt(var_g +
+ * 1e-5)), the values the gate used.
+ * Rounding to 16 bits: the input and the conv weights; the gated map as the
+ * squeeze's operand; the squeezed map [u | l] at its store; the output.  All
+ * sums are fp32 in a fixed order that depends on (h, w, c) alone, no atomics: a
+ * crop's bits do not depend on n.  The gate is z > 0.
+ * FAC_ERR_ARG: a null (x, packed, out, scratch) or misaligned (16 bytes)
+ * pointer, n <= 0, a bad dtype or pool, out overlapping x; FAC_ERR_SHAPE: c not
+ * one of 64, 128, 256, h or w outside 2..224 or odd with pool, n above 65535. */
+size_t fac_scconv_packed_bytes(int c);
+size_t fac_scconv_scratch_bytes(int n, int h, int w, int c);
+int fac_scconv_pack(int dtype, int c, const float* gamma, const float* beta, const float* kc, const float* squeeze1,
+                    const float* squeeze2, const float* gwc_w, const float* gwc_b, const float* pwc1,
+                    const float* pwc2, const float* scale, const float* shift, void* out);
+int fac_scconv(int dtype, const void* x, int n, int h, int w, int c, const void* packed, int pool, void* out,
+               float* stats_out, void* scratch, void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
