@@ -28,6 +28,10 @@ there).  ``VariantCViT`` is the one class body for all of them:
     scconv   ``fac_scconv``: ScConv -> BatchNorm -> ReLU (-> pool), with one
              scratch buffer kept per model for its sites, the entries of
              ``weights.SCCONV_VARIANTS`` (scconv.py);
+    odconv   ``fac_odconv``: ODConv2d -> BatchNorm -> ReLU (-> pool) in place of a
+             conv, or the bare block after a sequential, with one scratch buffer
+             kept per model for its sites, the entries of
+             ``weights.ODCONV_VARIANTS`` (odconv.py);
     ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
              (GGCA(x)) at the entry's site;
 
@@ -59,8 +63,8 @@ from torch import nn
 from . import _lib
 from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
 from .ops import TORCH16, fold_bn, pack_input
-from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, REPBN8_NAME, SCCONV_VARIANTS, VARIANT_NAMES, VARIANTS,
-                      family_entry, param_specs)
+from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, ODCONV_VARIANTS, REPBN8_NAME, SCCONV_VARIANTS,
+                      VARIANT_NAMES, VARIANTS, family_entry, param_specs)
 
 SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048)
@@ -108,9 +112,9 @@ def _init_tensor(shape, kind):
         return torch.zeros((), dtype=torch.long)
     if kind == "step":
         return torch.tensor(300000)
-    if kind in ("rmean", "beta", "lbias", "cbias"):
+    if kind in ("rmean", "beta", "lbias", "cbias", "od_arm", "od_rmean"):
         return torch.zeros(shape)
-    if kind in ("rvar", "gamma", "alpha"):
+    if kind in ("rvar", "gamma", "alpha", "od_arv", "od_rvar"):
         return torch.ones(shape)
     if kind == "emb":
         return torch.randn(shape)
@@ -137,17 +141,17 @@ def _pos_index(B: int, pos_index, device) -> torch.Tensor:
 
 # One launch of the stem.  labels: the values of stem_features' `upto` that stop
 # right after it ("after n entries of the table's layers", "features1", "smfa",
-# "ggca", "bfm", "mdfa"); H: the side of the map it runs on; ci, co: its input / output channels;
+# "ggca", "bfm", "mdfa", "odconv"); H: the side of the map it runs on; ci, co: its input / output channels;
 # pool, relu: fac_conv3x3's and fac_idwconv's epilogue; op: the ggca step's GGCA_OPS name.
 Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, False, None))
 
 
 def stem_plan(entry) -> list:
-    """The launches of one CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS or SCCONV_VARIANTS entry's
-    conv stem, in order (kinds: the module docstring's).  The first block is the
+    """The launches of one CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS or
+    ODCONV_VARIANTS entry's conv stem, in order (kinds: the module docstring's).  The first block is the
     fused stem224 if and only if the entry's first three layers are convs or
     DEConvs.  Where several blocks follow one sequential they run smfa, ggca,
-    bfm, mdfa (no reference forward has mdfa beside another block at one site)."""
+    bfm, mdfa, odconv (no reference forward has mdfa or the bare odconv beside another block at one site)."""
     layers = entry["layers"]
     seqs = [l[0] for l in layers]
     end = lambda s: len(layers) if s == "stem" else max(i for i, q in enumerate(seqs) if q == s) + 1  # noqa: E731
@@ -157,12 +161,14 @@ def stem_plan(entry) -> list:
     bfm_at = end(bfm[0]) if bfm is not None else None
     mdfa = entry.get("mdfa")
     mdfa_at = end(mdfa[0]) if mdfa is not None else None
+    od = entry.get("odconv")
+    od_at = end(od[0]) if od is not None else None
     f1 = end(seqs[0])
     fused = all(l[2] != "idw" for l in layers[:3])
     if fused:
         assert [l[3:5] + l[6:] for l in layers[:3]] == [(3, 32, True, False), (32, 32, True, False),
                                                          (32, 32, True, True)] and \
-            min(f1, ggca_at or 4, smfa_at or 4, bfm_at or 4, mdfa_at or 4) > 3
+            min(f1, ggca_at or 4, smfa_at or 4, bfm_at or 4, mdfa_at or 4, od_at or 4) > 3
         plan, H, done = [Step("stem224", (3,), 224, 3, 32, True, True)], 112, 3
     else:
         plan, H, done = [Step("pack32", (), 224, 3, 32)], 224, 0
@@ -172,6 +178,8 @@ def stem_plan(entry) -> list:
             plan.append(Step("idw", labels, H, co, co, pool, True))
         elif kind == "sc":
             plan.append(Step("scconv", labels, H, co, co, pool, True))
+        elif kind == "od":
+            plan.append(Step("odconv", labels, H, co, co, pool, relu))
         else:
             plan.append(Step("conv", labels, H, 32 if n == 1 else ci, co, pool, relu))
         if pool:
@@ -187,6 +195,9 @@ def stem_plan(entry) -> list:
         if n == mdfa_at:
             assert co == mdfa[1], (co, mdfa)
             plan.append(Step("mdfa", ("mdfa",), H, co, co))
+        if n == od_at:                         # the bare block: no BatchNorm, no ReLU, no pool
+            assert co == od[1], (co, od)
+            plan.append(Step("odconv", ("odconv",), H, co, co))
     return plan
 
 
@@ -194,7 +205,7 @@ def steps_upto(plan, upto) -> int:
     """How many steps of `plan` run for stem_features' `upto`: None all of them;
     an int n up to and including the n-th entry of the table's layers;
     "features1" the first sequential, before the block that follows it; "smfa" /
-    "ggca" / "bfm" / "mdfa" that block.  ValueError where the plan has no such stop: an int
+    "ggca" / "bfm" / "mdfa" / "odconv" that block.  ValueError where the plan has no such stop: an int
     inside the fused first block or past the last layer, a block the class lacks."""
     if upto is None:
         return len(plan)
@@ -217,7 +228,8 @@ class VariantCViT(nn.Module):
     def __init__(self, image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
-        if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS)):
+        if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS,
+                                                           ODCONV_VARIANTS)):
             raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -249,6 +261,8 @@ class VariantCViT(nn.Module):
         self._mdfa_outgrown = []
         self._scconv_scratch = None        # fac_scconv's, one buffer for all its sites, the same rule
         self._scconv_outgrown = []
+        self._odconv_scratch = None        # fac_odconv's, the same rule
+        self._odconv_outgrown = []
         self.eval()
 
     # ------------------------------------------------------------------ weights
@@ -281,9 +295,10 @@ class VariantCViT(nn.Module):
 
     def _fold(self, sd):
         """Per table layer its operands in fp32 on the host: (weight, bias) with
-        the DEConv and the BatchNorm folded, dconv.idw_fold's five, or
-        scconv.scconv_fold's dict."""
+        the DEConv and the BatchNorm folded, dconv.idw_fold's five,
+        scconv.scconv_fold's dict or odconv.odconv_fold's dict."""
         from .dconv import idw_fold
+        from .odconv import odconv_fold
         from .scconv import scconv_fold
         for seq, idx, kind, _ci, _co, bn, _relu, _pool in self.table["layers"]:
             p, q = f"{seq}.{idx}", f"{seq}.{bn}"
@@ -292,6 +307,9 @@ class VariantCViT(nn.Module):
                 continue
             if kind == "sc":
                 yield scconv_fold(sd, p, q)
+                continue
+            if kind == "od":
+                yield odconv_fold(sd, p, q)
                 continue
             w, b = (sd[p + ".weight"], sd[p + ".bias"]) if kind == "conv" else deconv_fold(sd, p)
             if bn is not None:
@@ -303,9 +321,12 @@ class VariantCViT(nn.Module):
     def folded_layers(self):
         """(weight, bias, relu, pool) per conv; for a table with InceptionDWConv2d
         layers, ("conv", weight, bias, pool) or ("idw", w_hw, w_w, w_h, scale, shift, pool); for one with
-        ScConv layers, ("conv", weight, bias, pool) or ("sc", scconv_fold's dict, pool)."""
+        ScConv layers, ("conv", weight, bias, pool) or ("sc", scconv_fold's dict, pool); for one with
+        ODConv layers, ("conv", weight, bias, pool) or ("od", odconv_fold's dict, pool)."""
         layers = self.table["layers"]
         ops = self._fold(self.state_dict())
+        if any(l[2] == "od" for l in layers):
+            return [("od", o, l[7]) if l[2] == "od" else ("conv", *o, l[7]) for l, o in zip(layers, ops)]
         if any(l[2] == "sc" for l in layers):
             return [("sc", o, l[7]) if l[2] == "sc" else ("conv", *o, l[7]) for l, o in zip(layers, ops)]
         if any(l[2] == "idw" for l in layers):
@@ -351,6 +372,8 @@ class VariantCViT(nn.Module):
         self._smfa16 = smfa16          # bound here: other.py imports this module
         from .scconv import scconv16, scconv_pack
         self._scconv16 = scconv16
+        from .odconv import odconv16, odconv_fold, odconv_pack
+        self._odconv16 = odconv16
         folded = list(self._fold(sd))
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         self._ggca = self._smfa = self._bfm = self._mdfa = None
@@ -368,6 +391,9 @@ class VariantCViT(nn.Module):
                 ops = tuple(t.to(device) for t in folded[s.labels[0] - 1])
             elif s.kind == "scconv":
                 ops = scconv_pack(folded[s.labels[0] - 1], self.dtype_name, device)
+            elif s.kind == "odconv":           # a table layer, or the bare top-level self.odconv
+                ops = odconv_pack(folded[s.labels[0] - 1] if s.labels != ("odconv",) else odconv_fold(sd, "odconv"),
+                                  self.dtype_name, device)
             elif s.kind == "smfa":
                 ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
             elif s.kind == "bfm":
@@ -440,17 +466,19 @@ class VariantCViT(nn.Module):
             self._mdfa_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
         return buf
 
-    def _scconv_scratch_for(self, B: int, device) -> torch.Tensor:
-        """fac_scconv's scratch for B crops: one buffer sized for the largest of
-        the class's ScConv sites (they run one after the other on one stream), kept
-        and grown like _scratch_for's."""
-        lib = _lib.load()
-        need = max(lib.fac_scconv_scratch_bytes(B, s.H, s.H, s.co) for s, _run, _ops in self._steps if s.kind == "scconv")
-        buf = self._scconv_scratch
+    def _site_scratch_for(self, kind: str, B: int, device) -> torch.Tensor:
+        """The scratch of fac_<kind> (scconv, odconv) for B crops: one buffer
+        (self._<kind>_scratch) sized for the largest of the class's sites of that
+        kind (they run one after the other on one stream), kept and grown like
+        _scratch_for's, the outgrown ones in self._<kind>_outgrown."""
+        size = getattr(_lib.load(), f"fac_{kind}_scratch_bytes")
+        need = max(size(B, s.H, s.H, s.co) for s, _run, _ops in self._steps if s.kind == kind)
+        buf = getattr(self, f"_{kind}_scratch")
         if buf is None or buf.numel() < need or buf.device != torch.device(device):
             if buf is not None:
-                self._scconv_outgrown.append(buf)
-            self._scconv_scratch = buf = torch.empty(need, dtype=torch.uint8, device=device)
+                getattr(self, f"_{kind}_outgrown").append(buf)
+            buf = torch.empty(need, dtype=torch.uint8, device=device)
+            setattr(self, f"_{kind}_scratch", buf)
         return buf
 
     def reserve(self, max_batch: int, device=None):
@@ -462,8 +490,9 @@ class VariantCViT(nn.Module):
                 self._scratch_for(int(max_batch), s, ops.device)
             elif s.kind == "mdfa":
                 self._mdfa_scratch_for(int(max_batch), s, ops.device)
-        if any(s.kind == "scconv" for s, _run, _ops in self._steps):
-            self._scconv_scratch_for(int(max_batch), dev)
+        for kind in ("scconv", "odconv"):
+            if any(s.kind == kind for s, _run, _ops in self._steps):
+                self._site_scratch_for(kind, int(max_batch), dev)
 
     # ------------------------------------------------------------------ the stem's launches
     # _step_<kind>(x, s, ops, u8, st) -> the step's output, a new tensor; x: the
@@ -501,7 +530,11 @@ class VariantCViT(nn.Module):
         return y
 
     def _step_scconv(self, x, s, ops, u8, st):
-        return self._scconv16(x, ops, self.dtype_name, pool=s.pool, scratch=self._scconv_scratch_for(x.shape[0], x.device))
+        return self._scconv16(x, ops, self.dtype_name, pool=s.pool, scratch=self._site_scratch_for("scconv", x.shape[0], x.device))
+
+    def _step_odconv(self, x, s, ops, u8, st):
+        return self._odconv16(x, ops, self.dtype_name, relu=s.relu, pool=s.pool,
+                              scratch=self._site_scratch_for("odconv", x.shape[0], x.device))
 
     def _step_smfa(self, x, s, ops, u8, st):
         return self._smfa16(x, ops, self.dtype_name, residual=True,

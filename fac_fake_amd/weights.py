@@ -872,7 +872,7 @@ _VARIANT_BLOCKS = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 256, 4), (256, 5
 def _variant_layers(split, kinds: str, bare26: bool = False):
     """The stem's layer list in the REPBN8_LAYERS format.  split: blocks per
     nn.Sequential; kinds: one letter per conv in order, "c" Conv2d or "d"
-    DEConv, "s" ScConv (SCCONV_VARIANTS); bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
+    DEConv, "s" ScConv (SCCONV_VARIANTS), "o" ODConv2d (ODCONV_VARIANTS); bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
     without BatchNorm or ReLU, a DEConv without BatchNorm (:390-392)."""
     kinds = kinds.replace(" ", "")
     names = ["features"] if len(split) == 1 else [f"features{i + 1}" for i in range(len(split))]
@@ -884,7 +884,7 @@ def _variant_layers(split, kinds: str, bare26: bool = False):
             idx, prev = 0, seq
         convs += 1 if bare26 and bi == 2 else 0
         for li in range(convs):
-            kind = {"c": "conv", "d": "deconv", "s": "sc"}[kinds[k]]
+            kind = {"c": "conv", "d": "deconv", "s": "sc", "o": "od"}[kinds[k]]
             k += 1
             ci, last = cin if li == 0 else cout, li == convs - 1
             if bare26 and bi == 2 and li == 2:
@@ -1170,8 +1170,75 @@ def _scconv_bn_specs(p, c):
             (f"{p}.running_var", (c,), "sc_rvar"), (f"{p}.num_batches_tracked", (), "nbt")]
 
 
+# ---------------------------------------------------------------- CViT model/other/ with ODConv
+# CViT-main/model/other/cvit_GGCA_ADD_ODConv.py and cvit_GGCA_ODConv.py.  The
+# first is the (4, 1) stem with four of its 3x3 convs replaced by ODConv2d(C, C,
+# 3) -> BatchNorm -> ReLU (:158-292: omni-dimensional dynamic convolution, four
+# candidate kernels mixed per crop by a softmax, with sigmoid attentions over
+# the input channels, the output channels and the nine taps, all from a 16-wide
+# bottleneck on the crop's channel means; odconv.py), at 64x112x112, 128x56x56
+# and 256x28x28 twice, x + GGCA(x) on the stem output and an unused top-level
+# self.odconv = ODConv2d(256, 256, 3).  The second is the plain stem with that
+# self.odconv called on the 256x14x14 output of features1, with no BatchNorm and
+# no ReLU after it, and x = GGCA(x) on the stem output.  A table of its own,
+# looked up fifth.  An entry is a CVIT_FAMILY entry whose layers may have the
+# kind "od" (cin = cout = C), plus
+#   odconv         (sequential it follows, C): the bare block is called there;
+#   odconv_unused  C of a self.odconv that is in the state_dict and never called.
+ODCONV_KINDS = "ccc coc coc coco cccc"
+ODCONV_VARIANTS = {
+    "cvit_GGCA_ADD_ODConv": dict(_entry(_variant_layers((4, 1), ODCONV_KINDS), _STEM_ADD, "layernorm", False),
+                                 odconv_unused=256),
+    "cvit_GGCA_ODConv": dict(_entry(_variant_layers((4, 1), _PLAIN_KINDS), ("stem", (512, 7, 7), "att"), "layernorm",
+                                    False), odconv=("features1", 256)),
+}
+ODCONV_NAMES = tuple(ODCONV_VARIANTS)
+ODCONV_KERNEL_NUM, ODCONV_ATT = 4, 16
+# Synthetic ODConv weights.  The reference's init (zero head biases, identity
+# BatchNorm) leaves all four attentions nearly constant, which would hide the
+# block.  Here the four W_k are independent He-uniform draws times ODCONV_GAIN:
+# the three sigmoids are about 1/2 each and the softmax mixes four independent
+# kernels, so a He-bound block would shrink its input about sixteen times.  fc
+# is +-sqrt(3 / C); the attention's BatchNorm has running_mean around
+# ODCONV_FC_MEAN[block] and running_var around the square of ODCONV_FC_STD[block],
+# the mean and deviation of fc p over the sixteen units on the fixture crops, so
+# that hid straddles the ReLU.  The channel, filter and spatial heads are drawn
+# in +-ODCONV_HEAD_GAIN with biases in +-ODCONV_HEAD_BIAS (logits over about
+# +-2), the kernel head in +-ODCONV_KERNEL_GAIN with biases in
+# +-ODCONV_KERNEL_BIAS (no kernel takes over, none dies).  The BatchNorm after a
+# block has running_var around the square of ODCONV_OUT_STD[its prefix] and
+# running_mean around ODCONV_OUT_MEAN[its prefix].  All four tables are measured
+# block by block on the reference classes with tools/make_golden_odconv.py
+# --calibrate (the unused odconv of cvit_GGCA_ADD_ODConv has the other class's
+# values: same key, same draw); the tool asserts the outcome.
+ODCONV_GAIN = 8.0
+ODCONV_HEAD_GAIN, ODCONV_HEAD_BIAS = 0.6, 1.0
+ODCONV_KERNEL_GAIN, ODCONV_KERNEL_BIAS = 0.3, 0.5
+ODCONV_FC_MEAN = {"features1.13": -0.217, "features1.23": -0.0773, "features1.33": -0.3326, "features1.39": -0.1357,
+                  "odconv": -0.2664}
+ODCONV_FC_STD = {"features1.13": 1.623, "features1.23": 1.024, "features1.33": 1.277, "features1.39": 0.6835, "odconv": 3.007}
+ODCONV_OUT_STD = {"features1.14": 1.918, "features1.24": 1.119, "features1.34": 1.102, "features1.40": 0.7997}
+ODCONV_OUT_MEAN = {"features1.14": 0.04675, "features1.24": 0.07572, "features1.34": 0.05849, "features1.40": -0.00978}
+
+
+def _odconv_specs(p, c):
+    a, h = f"{p}.attention", ODCONV_ATT
+    specs = [(f"{p}.weight", (ODCONV_KERNEL_NUM, c, c, 3, 3), "od_w"), (f"{a}.fc.weight", (h, c, 1, 1), "od_fc"),
+             (f"{a}.bn.weight", (h,), "gamma"), (f"{a}.bn.bias", (h,), "beta"), (f"{a}.bn.running_mean", (h,), "od_arm"),
+             (f"{a}.bn.running_var", (h,), "od_arv"), (f"{a}.bn.num_batches_tracked", (), "nbt")]
+    for head, n in (("channel", c), ("filter", c), ("spatial", 9)):
+        specs += [(f"{a}.{head}_fc.weight", (n, h, 1, 1), "od_head"), (f"{a}.{head}_fc.bias", (n,), "od_headb")]
+    return specs + [(f"{a}.kernel_fc.weight", (ODCONV_KERNEL_NUM, h, 1, 1), "od_khead"),
+                    (f"{a}.kernel_fc.bias", (ODCONV_KERNEL_NUM,), "od_kheadb")]
+
+
+def _odconv_bn_specs(p, c):
+    return [(f"{p}.weight", (c,), "gamma"), (f"{p}.bias", (c,), "beta"), (f"{p}.running_mean", (c,), "od_rmean"),
+            (f"{p}.running_var", (c,), "od_rvar"), (f"{p}.num_batches_tracked", (), "nbt")]
+
+
 def family_entry(name: str) -> dict:
-    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS', MDFA_VARIANTS' or SCCONV_VARIANTS'."""
+    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS', MDFA_VARIANTS', SCCONV_VARIANTS' or ODCONV_VARIANTS'."""
     if name in CVIT_FAMILY:
         return CVIT_FAMILY[name]
     if name in BFM_VARIANTS:
@@ -1180,8 +1247,10 @@ def family_entry(name: str) -> dict:
         return MDFA_VARIANTS[name]
     if name in SCCONV_VARIANTS:
         return SCCONV_VARIANTS[name]
+    if name in ODCONV_VARIANTS:
+        return ODCONV_VARIANTS[name]
     raise KeyError(f"unknown CViT variant {name!r}; known: "
-                   f"{', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES + SCCONV_NAMES)}")
+                   f"{', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES + SCCONV_NAMES + ODCONV_NAMES)}")
 
 
 def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
@@ -1194,6 +1263,9 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
             specs += [(f"{p}.weight", (co, ci, 3, 3), "conv"), (f"{p}.bias", (co,), "cbias")]
         elif kind == "sc":
             specs += _scconv_specs(p, co) + _scconv_bn_specs(f"{seq}.{bn}", co)
+            continue
+        elif kind == "od":
+            specs += _odconv_specs(p, co) + _odconv_bn_specs(f"{seq}.{bn}", co)
             continue
         else:
             specs += _deconv_specs(p, co) if kind == "deconv" else _idw_specs(p, co)
@@ -1226,6 +1298,9 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
         specs += _bn_specs("ggca.shared_conv.1", gc // 16)
         specs += [("ggca.shared_conv.3.weight", (gc, gc // 16, 1, 1), "conv"),
                   ("ggca.shared_conv.3.bias", (gc,), "cbias")]
+    od_c = entry["odconv"][1] if entry.get("odconv") is not None else entry.get("odconv_unused")
+    if od_c is not None:
+        specs += _odconv_specs("odconv", od_c)  # self.odconv: defined after ggca; called, or (odconv_unused) never
     if entry["deconv"]:
         specs += _deconv_specs("Deconv", 256)   # self.Deconv = DEConv(256): in the state_dict, never called
     if entry["smfa"] is not None:
@@ -1311,6 +1386,34 @@ def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]"
                 sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
             else:
                 sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
+        elif kind == "od_w":
+            a = float(ODCONV_GAIN * np.sqrt(6.0 / int(np.prod(shape[2:]))))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "od_fc":
+            a = float(np.sqrt(3.0 / shape[1]))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind in ("od_arm", "od_arv"):
+            blk = key[:-len(".attention.bn.running_mean")] if kind == "od_arm" else key[:-len(".attention.bn.running_var")]
+            mean, std = ODCONV_FC_MEAN.get(blk, 0.0), ODCONV_FC_STD.get(blk, 1.0)
+            if kind == "od_arm":
+                sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
+            else:
+                sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
+        elif kind == "od_head":
+            sd[key] = _u(key, shape, seed, -ODCONV_HEAD_GAIN, ODCONV_HEAD_GAIN)
+        elif kind == "od_headb":
+            sd[key] = _u(key, shape, seed, -ODCONV_HEAD_BIAS, ODCONV_HEAD_BIAS)
+        elif kind == "od_khead":
+            sd[key] = _u(key, shape, seed, -ODCONV_KERNEL_GAIN, ODCONV_KERNEL_GAIN)
+        elif kind == "od_kheadb":
+            sd[key] = _u(key, shape, seed, -ODCONV_KERNEL_BIAS, ODCONV_KERNEL_BIAS)
+        elif kind in ("od_rmean", "od_rvar"):
+            bn = key.rsplit(".", 1)[0]
+            std, mean = ODCONV_OUT_STD[bn], ODCONV_OUT_MEAN[bn]
+            if kind == "od_rmean":
+                sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
+            else:
+                sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
         elif kind == "mdfa_wt":
             sd[key] = _u(key, shape, seed, 0.0, 2.0 * MDFA_T_MEAN.get(shape[1] // 5, 1.0) / shape[1])
         else:
@@ -1378,3 +1481,11 @@ def scconv_param_specs(name: str, **kw):
 
 def make_scconv_state_dict(name: str = "cvit_GGCA_ADD_ScConv", seed: int = 0, **kw):
     return synthetic_state_dict(scconv_param_specs(name, **kw), seed)
+
+
+def odconv_param_specs(name: str, **kw):
+    return param_specs(ODCONV_VARIANTS[name], **kw)
+
+
+def make_odconv_state_dict(name: str = "cvit_GGCA_ADD_ODConv", seed: int = 0, **kw):
+    return synthetic_state_dict(odconv_param_specs(name, **kw), seed)

@@ -613,6 +613,50 @@ int fac_scconv_pack(int dtype, int c, const float* gamma, const float* beta, con
 int fac_scconv(int dtype, const void* x, int n, int h, int w, int c, const void* packed, int pool, void* out,
                float* stats_out, void* scratch, void* stream);
 
+/* ODConv2d(c, c, 3, padding 1) -> affine(scale, shift) -> optional ReLU ->
+ * optional 2x2 max-pool of CViT-main/model/other/cvit_GGCA_ADD_ODConv.py:158-292
+ * (odconv.hip; kernel_num 4, attention width 16, temperature 1, no conv bias) on
+ * a 16-bit channels-last map x [n][h][w][c] -> out [n][h][w][c], pooled
+ * [n][h/2][w/2][c].  Per crop: p = the channel means, hid = ReLU(bn_scale (fc p)
+ * + bn_shift), ca = sigmoid(channel_fc hid + channel_b), fa = sigmoid(filter_fc
+ * hid + filter_b), sa = sigmoid(spatial_fc hid + spatial_b), ka =
+ * softmax(kernel_fc hid + kernel_b), and
+ *   out[o] = act(fa[o] sum_tap sa[tap] sum_i (sum_k ka[k] W[k][o][i][tap]) ca[i] x[i, tap] * scale[o] + shift[o]):
+ * the conv weights differ per crop.
+ * fac_odconv_pack (host pointers, fp32 in) takes W [4][c][c][3][3], fc [16][c],
+ * bn_scale, bn_shift [16] (the attention's BatchNorm, folded), channel_fc
+ * [c][16], channel_b [c], filter_fc [c][16], filter_b [c], spatial_fc [9][16],
+ * spatial_b [9], kernel_fc [4][16], kernel_b [4], scale, shift [c] (the BatchNorm
+ * that follows, folded; 1 and 0 for a bare block) and writes
+ * fac_odconv_packed_bytes(c) bytes (0 for a bad c); everything stays fp32 in
+ * the blob, which is the same for both dtypes.  packed is that blob in device
+ * memory.  scratch: fac_odconv_scratch_bytes(n, h, w, c) bytes (0 for a bad
+ * shape), at most 48 MiB of aggregated weights plus n (ceil(h w / 512) c + 2 c +
+ * 16) floats.  The call allocates nothing, runs 2 + 2 ceil(n / k) launches on
+ * `stream` (k = the crops whose aggregated weights fit the 48 MiB: 682, 170, 42
+ * for c = 64, 128, 256; fac_odconv_chunk(n, c) gives min(n, k), 0 for a bad n or
+ * c) and can be captured.
+ * relu: 1 ReLU, 0 identity.  att_out: null, or device fp32 [n][2c + 13] that
+ * receives ca | fa | sa | ka as the conv used them.
+ * Rounding to 16 bits: the input; the aggregated per-crop weight sa[tap] ca[i]
+ * sum_k ka[k] W_k, once (the W_k themselves are never rounded); the output.  The
+ * means, hid, the four attentions, fa, scale, shift, the aggregation and all
+ * accumulation are fp32, every sum in a fixed order that depends on (h, w, c)
+ * alone, no atomics: a crop's bits do not depend on n or on its position.
+ * FAC_ERR_ARG: a null (x, packed, out, scratch) or misaligned (16 bytes; att_out
+ * 4) pointer, n <= 0, a bad dtype, relu or pool, out overlapping x;
+ * FAC_ERR_SHAPE: c not one of 64, 128, 256, h or w outside 2..224 or odd with
+ * pool, n above 65535. */
+size_t fac_odconv_packed_bytes(int c);
+size_t fac_odconv_scratch_bytes(int n, int h, int w, int c);
+int fac_odconv_chunk(int n, int c);
+int fac_odconv_pack(int dtype, int c, const float* weight, const float* fc, const float* bn_scale, const float* bn_shift,
+                    const float* channel_fc, const float* channel_b, const float* filter_fc, const float* filter_b,
+                    const float* spatial_fc, const float* spatial_b, const float* kernel_fc, const float* kernel_b,
+                    const float* scale, const float* shift, void* out);
+int fac_odconv(int dtype, const void* x, int n, int h, int w, int c, const void* packed, int relu, int pool, void* out,
+               float* att_out, void* scratch, void* stream);
+
 /* Row-wise sigmoid of logits (the per-logit pred_sig of the heads). */
 int fac_sigmoid(const float* x, float* y, int n, void* stream);
 
