@@ -32,6 +32,9 @@ there).  ``VariantCViT`` is the one class body for all of them:
              conv, or the bare block after a sequential, with one scratch buffer
              kept per model for its sites, the entries of
              ``weights.ODCONV_VARIANTS`` (odconv.py);
+    wt       ``fac_wtconv``: WTConv2d -> BatchNorm -> ReLU (-> pool) in one
+             launch with no scratch, the entries of ``weights.WTCONV_VARIANTS``
+             (wtconv.py);
     ggca     ``fac_ggca_apply`` (x * GGCA(x), x + GGCA(x)) or ``fac_ggca_scale``
              (GGCA(x)) at the entry's site;
 
@@ -64,7 +67,7 @@ from . import _lib
 from .cvit import MAX_SLOTS, _Node, reference_mask_poisons, weight_versions
 from .ops import TORCH16, fold_bn, pack_input
 from .weights import (BFM_VARIANTS, CVIT_FAMILY, MDFA_VARIANTS, ODCONV_VARIANTS, REPBN8_NAME, SCCONV_VARIANTS,
-                      VARIANT_NAMES, VARIANTS, family_entry, param_specs)
+                      VARIANT_NAMES, VARIANTS, WTCONV_VARIANTS, family_entry, param_specs)
 
 SUPPORTED = dict(image_size=224, patch_size=7, num_classes=2, channels=512, dim=1024, depth=6, heads=8,
                  mlp_dim=2048)
@@ -147,8 +150,8 @@ Step = namedtuple("Step", "kind labels H ci co pool relu op", defaults=(False, F
 
 
 def stem_plan(entry) -> list:
-    """The launches of one CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS or
-    ODCONV_VARIANTS entry's conv stem, in order (kinds: the module docstring's).  The first block is the
+    """The launches of one CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS,
+    ODCONV_VARIANTS or WTCONV_VARIANTS entry's conv stem, in order (kinds: the module docstring's).  The first block is the
     fused stem224 if and only if the entry's first three layers are convs or
     DEConvs.  Where several blocks follow one sequential they run smfa, ggca,
     bfm, mdfa, odconv (no reference forward has mdfa or the bare odconv beside another block at one site)."""
@@ -164,7 +167,7 @@ def stem_plan(entry) -> list:
     od = entry.get("odconv")
     od_at = end(od[0]) if od is not None else None
     f1 = end(seqs[0])
-    fused = all(l[2] != "idw" for l in layers[:3])
+    fused = all(l[2] not in ("idw", "wt") for l in layers[:3])
     if fused:
         assert [l[3:5] + l[6:] for l in layers[:3]] == [(3, 32, True, False), (32, 32, True, False),
                                                          (32, 32, True, True)] and \
@@ -180,6 +183,8 @@ def stem_plan(entry) -> list:
             plan.append(Step("scconv", labels, H, co, co, pool, True))
         elif kind == "od":
             plan.append(Step("odconv", labels, H, co, co, pool, relu))
+        elif kind == "wt":
+            plan.append(Step("wt", labels, H, co, co, pool, True))
         else:
             plan.append(Step("conv", labels, H, 32 if n == 1 else ci, co, pool, relu))
         if pool:
@@ -229,7 +234,7 @@ class VariantCViT(nn.Module):
                  mlp_dim=2048, *, dtype: str = "fp16"):
         super().__init__()
         if not any(self.variant in table for table in (CVIT_FAMILY, BFM_VARIANTS, MDFA_VARIANTS, SCCONV_VARIANTS,
-                                                           ODCONV_VARIANTS)):
+                                                           ODCONV_VARIANTS, WTCONV_VARIANTS)):
             raise TypeError("build a variant with variants.variant_class(name)")
         cfg = dict(image_size=image_size, patch_size=patch_size, num_classes=num_classes, channels=channels, dim=dim,
                    depth=depth, heads=heads, mlp_dim=mlp_dim)
@@ -273,6 +278,12 @@ class VariantCViT(nn.Module):
                 tot = float(torch.as_tensor(g).detach().float().sum())
                 if tot == 0.0 or tot != tot or tot in (float("inf"), float("-inf")):
                     raise ValueError(f"{seq}.{idx}.SRU.gn.weight sums to {tot}: ScConv divides by it")
+            if kind == "wt":              # wt_levels 1 only: a deeper WTConv2d's keys are refused, not ignored
+                deeper = [k for k in state_dict if k.startswith(f"{seq}.{idx}.wavelet_convs.") and
+                          not k.startswith(f"{seq}.{idx}.wavelet_convs.0.")]
+                if deeper:
+                    raise ValueError(f"{seq}.{idx} has more than one wavelet level ({deeper[0]}); the gfx950 WTConv2d "
+                                     "implements wt_levels=1")
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
         self._prep = None
         return out
@@ -296,10 +307,11 @@ class VariantCViT(nn.Module):
     def _fold(self, sd):
         """Per table layer its operands in fp32 on the host: (weight, bias) with
         the DEConv and the BatchNorm folded, dconv.idw_fold's five,
-        scconv.scconv_fold's dict or odconv.odconv_fold's dict."""
+        scconv.scconv_fold's dict, odconv.odconv_fold's dict or wtconv.wt_fold's dict."""
         from .dconv import idw_fold
         from .odconv import odconv_fold
         from .scconv import scconv_fold
+        from .wtconv import wt_fold
         for seq, idx, kind, _ci, _co, bn, _relu, _pool in self.table["layers"]:
             p, q = f"{seq}.{idx}", f"{seq}.{bn}"
             if kind == "idw":
@@ -310,6 +322,9 @@ class VariantCViT(nn.Module):
                 continue
             if kind == "od":
                 yield odconv_fold(sd, p, q)
+                continue
+            if kind == "wt":
+                yield wt_fold(sd, p, q)
                 continue
             w, b = (sd[p + ".weight"], sd[p + ".bias"]) if kind == "conv" else deconv_fold(sd, p)
             if bn is not None:
@@ -322,9 +337,12 @@ class VariantCViT(nn.Module):
         """(weight, bias, relu, pool) per conv; for a table with InceptionDWConv2d
         layers, ("conv", weight, bias, pool) or ("idw", w_hw, w_w, w_h, scale, shift, pool); for one with
         ScConv layers, ("conv", weight, bias, pool) or ("sc", scconv_fold's dict, pool); for one with
-        ODConv layers, ("conv", weight, bias, pool) or ("od", odconv_fold's dict, pool)."""
+        ODConv layers, ("conv", weight, bias, pool) or ("od", odconv_fold's dict, pool); for one with
+        WTConv layers, ("conv", weight, bias, pool) or ("wt", wt_fold's dict, pool)."""
         layers = self.table["layers"]
         ops = self._fold(self.state_dict())
+        if any(l[2] == "wt" for l in layers):
+            return [("wt", o, l[7]) if l[2] == "wt" else ("conv", *o, l[7]) for l, o in zip(layers, ops)]
         if any(l[2] == "od" for l in layers):
             return [("od", o, l[7]) if l[2] == "od" else ("conv", *o, l[7]) for l, o in zip(layers, ops)]
         if any(l[2] == "sc" for l in layers):
@@ -374,6 +392,8 @@ class VariantCViT(nn.Module):
         self._scconv16 = scconv16
         from .odconv import odconv16, odconv_fold, odconv_pack
         self._odconv16 = odconv16
+        from .wtconv import wt_pack, wtconv16
+        self._wtconv16 = wtconv16
         folded = list(self._fold(sd))
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         self._ggca = self._smfa = self._bfm = self._mdfa = None
@@ -394,6 +414,8 @@ class VariantCViT(nn.Module):
             elif s.kind == "odconv":           # a table layer, or the bare top-level self.odconv
                 ops = odconv_pack(folded[s.labels[0] - 1] if s.labels != ("odconv",) else odconv_fold(sd, "odconv"),
                                   self.dtype_name, device)
+            elif s.kind == "wt":
+                ops = wt_pack(folded[s.labels[0] - 1], device)
             elif s.kind == "smfa":
                 ops = self._smfa = smfa_pack(smfa_fold(sd), self.dtype_name, device)
             elif s.kind == "bfm":
@@ -535,6 +557,9 @@ class VariantCViT(nn.Module):
     def _step_odconv(self, x, s, ops, u8, st):
         return self._odconv16(x, ops, self.dtype_name, relu=s.relu, pool=s.pool,
                               scratch=self._site_scratch_for("odconv", x.shape[0], x.device))
+
+    def _step_wt(self, x, s, ops, u8, st):
+        return self._wtconv16(x, ops, self.dtype_name, pool=s.pool)
 
     def _step_smfa(self, x, s, ops, u8, st):
         return self._smfa16(x, ops, self.dtype_name, residual=True,

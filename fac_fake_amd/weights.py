@@ -872,7 +872,7 @@ _VARIANT_BLOCKS = [(3, 32, 3), (32, 64, 3), (64, 128, 3), (128, 256, 4), (256, 5
 def _variant_layers(split, kinds: str, bare26: bool = False):
     """The stem's layer list in the REPBN8_LAYERS format.  split: blocks per
     nn.Sequential; kinds: one letter per conv in order, "c" Conv2d or "d"
-    DEConv, "s" ScConv (SCCONV_VARIANTS), "o" ODConv2d (ODCONV_VARIANTS); bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
+    DEConv, "s" ScConv (SCCONV_VARIANTS), "o" ODConv2d (ODCONV_VARIANTS), "w" WTConv2d (WTCONV_VARIANTS); bare26: the third block is the RepBn8 one, conv, DEConv, a Conv2d
     without BatchNorm or ReLU, a DEConv without BatchNorm (:390-392)."""
     kinds = kinds.replace(" ", "")
     names = ["features"] if len(split) == 1 else [f"features{i + 1}" for i in range(len(split))]
@@ -884,7 +884,7 @@ def _variant_layers(split, kinds: str, bare26: bool = False):
             idx, prev = 0, seq
         convs += 1 if bare26 and bi == 2 else 0
         for li in range(convs):
-            kind = {"c": "conv", "d": "deconv", "s": "sc", "o": "od"}[kinds[k]]
+            kind = {"c": "conv", "d": "deconv", "s": "sc", "o": "od", "w": "wt"}[kinds[k]]
             k += 1
             ci, last = cin if li == 0 else cout, li == convs - 1
             if bare26 and bi == 2 and li == 2:
@@ -1237,8 +1237,85 @@ def _odconv_bn_specs(p, c):
             (f"{p}.running_var", (c,), "od_rvar"), (f"{p}.num_batches_tracked", (), "nbt")]
 
 
+# ---------------------------------------------------------------- CViT model/other/ with WTConv
+# CViT-main/model/other/cvit_GGCA_ADD_WTConv.py: the base CViT's one `features`
+# Sequential with nine of its 3x3 convs replaced by WTConv2d(C) -> BatchNorm ->
+# ReLU (:226-317 with kernel_size 5, wt_levels 1, db1: a depthwise 5x5 on the
+# four Haar subbands at half resolution, transformed back and added to a
+# depthwise 5x5 on the map itself; wtconv.py), two each on 32x224x224,
+# 64x112x112 and 128x56x56 and three on 256x28x28, and x + GGCA(x) on the stem
+# output.  A table of its own, looked up sixth.  An entry is a CVIT_FAMILY entry
+# whose layers may have the kind "wt" (cin = cout = C).
+WTCONV_KINDS = "cww cww cww cwww cccc"
+WTCONV_VARIANTS = {
+    "cvit_GGCA_ADD_WTConv": _entry(_variant_layers((5,), WTCONV_KINDS), _STEM_ADD, "layernorm", False),
+}
+WTCONV_NAMES = tuple(WTCONV_VARIANTS)
+# Synthetic WTConv weights.  wt_filter and iwt_filter are the db1 filters the
+# reference builds (create_wavelet_filter: outer products of [2^-1/2, 2^-1/2]
+# and [2^-1/2, -2^-1/2] in fp32, +-0.5 up to rounding; db1_filters).  The
+# depthwise taps are drawn in +-a, a = gain sqrt(3 / 25) (an L2 gain of `gain`
+# over the 25 taps).  They are symmetric about 0 on purpose: the layer is
+# depthwise and its BatchNorm statistics below are one figure per layer, so
+# taps with a positive sum give every channel a mean of its own, the channels
+# below the layer's mean die in the ReLU, and a dead channel stays dead through
+# the following depthwise layers (213 of 256 channels at features.39 with the
+# InceptionDWConv2d draw; at most 18 with this one).  base_scale is
+# drawn in [0.5, 1.5] and wavelet_scale in [0.05, 0.15] (the reference starts
+# them at 1 and 0.1), a quarter of either negative; WTCONV_WAVE_GAIN makes up for
+# the 0.1, so that neither path is lost in the other's rounding.  The BatchNorm
+# after a block has running_var around the square of WTCONV_OUT_STD[its prefix]
+# and running_mean around WTCONV_OUT_MEAN[its prefix], both measured block by
+# block on the fixture crops with tools/make_golden_wtconv.py --calibrate, so
+# that the activations stay O(1) through the nine layers.  The tool asserts the
+# outcome.
+WTCONV_BASE_GAIN = 1.0
+WTCONV_WAVE_GAIN = 10.0
+WTCONV_OUT_STD = {"features.4": 1.895, "features.7": 1.236, "features.14": 1.46, "features.17": 1.092, "features.24": 1.12,
+                  "features.27": 0.7872, "features.34": 1.431, "features.37": 0.9285, "features.40": 0.6053}
+WTCONV_OUT_MEAN = {"features.4": 0.06618, "features.7": 0.06642, "features.14": 0.1658, "features.17": -0.03757,
+                   "features.24": -0.05216, "features.27": 0.06356, "features.34": -0.01779, "features.37": 0.02346,
+                   "features.40": -0.05707}
+
+
+def db1_filters(c: int):
+    """(wt_filter, iwt_filter) [4c, 1, 2, 2] fp32 as WTConv2d(c) builds them for
+    'db1' (create_wavelet_filter :167-201 with PyWavelets' dec_lo = rec_lo =
+    [r, r], dec_hi = [-r, r], rec_hi = [r, -r], r = 2^-1/2): row 4ch + k is the
+    outer product lo x lo, lo x hi (rows), hi x lo, hi x hi, every product
+    taken in fp32."""
+    r = np.float32(2.0 ** -0.5)
+    out = []
+    for lo, hi in ((np.array([r, r], np.float32), np.array([r, -r], np.float32)),) * 2:   # reversed dec_*; flipped rec_*
+        f = np.stack([lo[None, :] * lo[:, None], lo[None, :] * hi[:, None], hi[None, :] * lo[:, None],
+                      hi[None, :] * hi[:, None]]).astype(np.float32)
+        out.append(np.tile(f[:, None], (c, 1, 1, 1)))
+    return out[0], out[1]
+
+
+def _quarter_negative(name, shape, seed, lo, hi):
+    """Magnitudes in [lo, hi), a quarter of the entries negative (an independent draw)."""
+    n = int(np.prod(shape))
+    mag = np.float32(lo) + np.float32(hi - lo) * np.abs(uniform(name, n, seed))
+    return np.where(uniform(name + "/sign", n, seed) < -0.5, -mag, mag).astype(np.float32).reshape(shape)
+
+
+def _wtconv_specs(p, c):
+    return [(f"{p}.wt_filter", (4 * c, 1, 2, 2), "wt_dec"), (f"{p}.iwt_filter", (4 * c, 1, 2, 2), "wt_rec"),
+            (f"{p}.base_conv.weight", (c, 1, 5, 5), "wt_base"), (f"{p}.base_conv.bias", (c,), "cbias"),
+            (f"{p}.base_scale.weight", (1, c, 1, 1), "wt_bscale"),
+            (f"{p}.wavelet_convs.0.weight", (4 * c, 1, 5, 5), "wt_wave"),
+            (f"{p}.wavelet_scale.0.weight", (1, 4 * c, 1, 1), "wt_wscale")]
+
+
+def _wtconv_bn_specs(p, c):
+    return [(f"{p}.weight", (c,), "gamma"), (f"{p}.bias", (c,), "beta"), (f"{p}.running_mean", (c,), "wt_rmean"),
+            (f"{p}.running_var", (c,), "wt_rvar"), (f"{p}.num_batches_tracked", (), "nbt")]
+
+
 def family_entry(name: str) -> dict:
-    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS', MDFA_VARIANTS', SCCONV_VARIANTS' or ODCONV_VARIANTS'."""
+    """The table entry of one class: CVIT_FAMILY's, BFM_VARIANTS', MDFA_VARIANTS', SCCONV_VARIANTS', ODCONV_VARIANTS' or
+    WTCONV_VARIANTS'."""
     if name in CVIT_FAMILY:
         return CVIT_FAMILY[name]
     if name in BFM_VARIANTS:
@@ -1249,8 +1326,10 @@ def family_entry(name: str) -> dict:
         return SCCONV_VARIANTS[name]
     if name in ODCONV_VARIANTS:
         return ODCONV_VARIANTS[name]
+    if name in WTCONV_VARIANTS:
+        return WTCONV_VARIANTS[name]
     raise KeyError(f"unknown CViT variant {name!r}; known: "
-                   f"{', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES + SCCONV_NAMES + ODCONV_NAMES)}")
+                   f"{', '.join(FAMILY_NAMES + BFM_NAMES + MDFA_NAMES + SCCONV_NAMES + ODCONV_NAMES + WTCONV_NAMES)}")
 
 
 def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=512, patch_size=7):
@@ -1266,6 +1345,9 @@ def param_specs(entry, dim=1024, depth=6, mlp_dim=2048, num_classes=2, channels=
             continue
         elif kind == "od":
             specs += _odconv_specs(p, co) + _odconv_bn_specs(f"{seq}.{bn}", co)
+            continue
+        elif kind == "wt":
+            specs += _wtconv_specs(p, co) + _wtconv_bn_specs(f"{seq}.{bn}", co)
             continue
         else:
             specs += _deconv_specs(p, co) if kind == "deconv" else _idw_specs(p, co)
@@ -1414,6 +1496,22 @@ def synthetic_state_dict(specs, seed: int = 0) -> "OrderedDict[str, np.ndarray]"
                 sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
             else:
                 sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
+        elif kind in ("wt_dec", "wt_rec"):
+            sd[key] = db1_filters(shape[0] // 4)[kind == "wt_rec"]
+        elif kind in ("wt_base", "wt_wave"):
+            a = float((WTCONV_BASE_GAIN if kind == "wt_base" else WTCONV_WAVE_GAIN) * np.sqrt(3.0 / 25.0))
+            sd[key] = _u(key, shape, seed, -a, a)
+        elif kind == "wt_bscale":
+            sd[key] = _quarter_negative(key, shape, seed, 0.5, 1.5)
+        elif kind == "wt_wscale":
+            sd[key] = _quarter_negative(key, shape, seed, 0.05, 0.15)
+        elif kind in ("wt_rmean", "wt_rvar"):
+            bn = key.rsplit(".", 1)[0]
+            std, mean = WTCONV_OUT_STD.get(bn, 1.0), WTCONV_OUT_MEAN.get(bn, 0.0)
+            if kind == "wt_rmean":
+                sd[key] = (np.float32(mean) + np.float32(std) * _u(key, shape, seed, -0.1, 0.1)).astype(np.float32)
+            else:
+                sd[key] = (np.float32(std * std) * _u(key, shape, seed, 0.8, 1.2)).astype(np.float32)
         elif kind == "mdfa_wt":
             sd[key] = _u(key, shape, seed, 0.0, 2.0 * MDFA_T_MEAN.get(shape[1] // 5, 1.0) / shape[1])
         else:
@@ -1489,3 +1587,11 @@ def odconv_param_specs(name: str, **kw):
 
 def make_odconv_state_dict(name: str = "cvit_GGCA_ADD_ODConv", seed: int = 0, **kw):
     return synthetic_state_dict(odconv_param_specs(name, **kw), seed)
+
+
+def wtconv_param_specs(name: str = "cvit_GGCA_ADD_WTConv", **kw):
+    return param_specs(WTCONV_VARIANTS[name], **kw)
+
+
+def make_wtconv_state_dict(name: str = "cvit_GGCA_ADD_WTConv", seed: int = 0, **kw):
+    return synthetic_state_dict(wtconv_param_specs(name, **kw), seed)

@@ -495,6 +495,38 @@ int fac_avgpool_f32(int dtype, const void* x, int n, int s, int c, float* y, voi
 int fac_idwconv(int dtype, const void* in, void* out, int n, int h, int w, int c, const float* w_hw, const float* w_w,
                 const float* w_h, const float* scale, const float* shift, int pool, void* stream);
 
+/* WTConv2d(c, kernel_size 5, wt_levels 1) -> BatchNorm2d (eval) -> ReLU
+ * (-> MaxPool2d(2,2) if pool) of
+ * CViT-main/model/other/cvit_GGCA_ADD_WTConv.py:167-328 in one launch
+ * (wtconv.hip).  in [n][h][w][c] -> out [n][h'][w'][c] (h' = h/2, w' = w/2
+ * with pool), 16-bit channels-last, 16-byte aligned, h and w even.  Per
+ * channel ch, cross-correlation as in F.conv2d, k = 0..3, i, j in {0, 1}:
+ *   s_k[y][x]     = sum_ij dwt[ch][k][i][j] in[2y+i][2x+j]           (half resolution)
+ *   t_k           = depthwise 5x5 of s_k with wtaps[ch][k], zero padding 2
+ *                   at the half-resolution border
+ *   u[2y+i][2x+j] = sum_k iwt[ch][k][i][j] t_k[y][x]
+ *   b             = depthwise 5x5 of in with btaps[ch], zero padding 2
+ *   out           = maxpool?(relu(scale[ch] * (u + b) + shift[ch]))
+ * The operands are fp32 device arrays, 4-byte aligned, with the channel split
+ * as ch = 4 * quad + e and e innermost, so that one wave's four channels are
+ * one contiguous run:
+ *   dwt, iwt  [c/4][4 k][4 = i*2+j][4 e]   the state_dict's wt_filter / iwt_filter [4c][1][2][2], row 4ch + k
+ *   wtaps     [c/4][4 k][25 = dy*5+dx][4 e]  wavelet_convs.0.weight [4c][1][5][5] times wavelet_scale.0.weight
+ *   btaps     [c/4][25][4 e]                 base_conv.weight [c][1][5][5] times base_scale.weight
+ *   scale, shift [c]    scale = gamma / sqrt(var + eps), shift = beta - mean *
+ *                       scale + base_scale * base_conv.bias * scale
+ * Every sum is an fp32 fma chain from 0 in index order (ij, then the 25 taps
+ * row-major, then k), then u + b, fma(scale, ., shift), ReLU, the window max
+ * and the only rounding, at the store: the subbands and t_k stay fp32.  A
+ * pixel outside the map enters as 0 (it contributes 0, never shift); for even
+ * sides that is also the reference's zero padding of the subbands.  No
+ * scratch, no atomics; a crop's output does not depend on n.
+ * FAC_ERR_ARG: a null or misaligned pointer, a bad dtype, a pool flag other
+ * than 0 or 1, n <= 0; FAC_ERR_SHAPE: c no multiple of 32 or outside 32..256,
+ * h or w odd or outside 2..224. */
+int fac_wtconv(int dtype, const void* in, void* out, int n, int h, int w, int c, const float* dwt, const float* wtaps,
+               const float* iwt, const float* btaps, const float* scale, const float* shift, int pool, void* stream);
+
 /* SMFA(x) or x + SMFA(x) of CViT-main/model/other/cvit_GGCA_SMFA.py:160-203
  * (smfa.hip) on a 16-bit channels-last map x [n][h][w][c] -> out [n][h][w][c],
  * for 8 <= h, w <= 15, where the block's adaptive max-pool is the per-channel
